@@ -7,10 +7,16 @@ batch of synthetic pictures already resident in HBM (B independent 
 sharing a reference set).  Workload: SURVEY config 3, 1080p (120x68 MBs) IPPP Main P
 pictures, B = 1024 per GPU (the order-dependent walks need many pictures in flight).
 
+A plain run sets the batch up, warms up, times `--steps` steps and prints the line; with
+`--dump-outputs DIR` it then writes what the last step left in the output planes (three whole
+pictures and a seeded sample over the batch, float32 .npy).  `--full` adds everything beside the
+headline: the oracle check before timing, the CPU baselines, the latency chain, the per-kernel
+roofline split with the PMC traffic, the measured copy peak, and the N > 1 extras below.
+
 N > 1 GPUs (default): the headline workload as N replicas (config 3 pictures, B per rank, no
 collective: disable_deblocking_filter_idc 0 chains every MB of a picture through the loop filter,
 deblock.cc:547-551), value = all ranks' MBs / the slowest rank's time -- the same workload as the
-one-GPU line, so the scaling curve compares like with like.  Beside it in the same line,
+one-GPU line, so the scaling curve compares like with like.  Beside it in the same line with --full,
 `slice_sharded`: chain mode on config 5 (2160p High B pictures, 8 slices,
 disable_deblocking_filter_idc 2), K = 32 x N dependent chains advance one picture per step, each
 rank decodes its band of slices of every picture, and the rows of the other bands that its next
@@ -135,6 +141,97 @@ def kernel_bytes(pics, nmb):
         intra += int(r[is_intra & ~pcm].sum())
         inter += int(r[~is_intra | pcm].sum())
     return [inter, intra, len(pics) * nmb * 384]
+
+
+SETUP_THREADS = 16      # worker threads of the batch set-up (bounded: a shared host shows more CPUs than a job gets)
+SETUP_CHUNK = 16        # pictures a worker generates and packs at a time
+
+
+def packed_chunks(L, cfg, index, with_kernel_bytes: bool):
+    """The batch's pictures `index` generated and packed (batch.pack) in chunks by worker threads
+    (the C generator and numpy's copies release the GIL).  Each chunk: its packed host arrays, its
+    SURVEY 8(d) read / write bytes and, on request, its kernel_bytes split."""
+    from concurrent.futures import ThreadPoolExecutor
+    import h264r
+    from h264r import batch as B
+    from h264r import synth
+    quant = h264r.quant_flat()
+    nmb = cfg.width_mbs * cfg.height_mbs
+
+    def chunk(idx):
+        pics = [synth.picture(L, cfg, i) for i in idx]
+        rd = wr = 0
+        for p in pics:
+            r, w = synth.algo_bytes(L, p)
+            rd, wr = rd + r, wr + w
+        return dict(host=B.pack(pics, quant), rd=rd, wr=wr,
+                    kbytes=kernel_bytes(pics, nmb) if with_kernel_bytes else None)
+    parts = [index[i: i + SETUP_CHUNK] for i in range(0, len(index), SETUP_CHUNK)]
+    with ThreadPoolExecutor(max(1, min(SETUP_THREADS, os.cpu_count() or 1))) as pool:
+        return list(pool.map(chunk, parts))
+
+
+def chunks_to_device(chunks, n: int, ref_planes_ptr):
+    """batch.to_device over packed_chunks' output: the chunks land one after the other in the
+    batch's device arrays, the level-pool offsets of each moved by the levels before it -- the
+    bytes batch.pack + batch.to_device give for the whole list of pictures."""
+    import torch
+    from h264r import _abi as A
+    from h264r import batch as B
+    host0 = chunks[0]["host"]
+    assert all(c["host"]["stride"] == host0["stride"] for c in chunks)
+    keys = ("mbs", "levels", "mv", "ref_idx", "slices", "pics", "quant")
+    t = {k: torch.empty(sum(c["host"][k].nbytes for c in chunks), dtype=torch.uint8, device="cuda") for k in keys}
+    at = dict.fromkeys(keys, 0)
+    off = 0
+    mbaff = True
+    for c in chunks:
+        h = c["host"]
+        h["mbs"]["coef_off"] += off
+        off += len(h["levels"])
+        mbaff &= bool((h["pics"]["structure"] == A.MBAFF_FRAME).all())
+        for k in keys:
+            a = np.ascontiguousarray(h[k]).view(np.uint8).reshape(-1)
+            t[k][at[k]: at[k] + a.size].copy_(torch.from_numpy(a))
+            at[k] += a.size
+    # the output planes and the descriptor as batch.to_device makes them
+    W, H, fmt = host0["W"], host0["H"], host0["chroma_format"]
+    cw, ch = A.chroma_mb(fmt)
+    for k, size in (("out_y", 256 * W * H), ("out_u", cw * ch * W * H), ("out_v", cw * ch * W * H)):
+        t[k] = torch.zeros((n, size), dtype=torch.uint8, device="cuda")
+    b = A.Batch()
+    b.num_pics, b.width_mbs, b.height_mbs, b.slice_stride = n, W, H, host0["stride"]
+    for k in t:
+        setattr(b, k, t[k].data_ptr())
+    b.ref_planes = ref_planes_ptr
+    b.mbaff = int(mbaff)
+    return B.DeviceBatch(b, n, W, H, t, fmt)
+
+
+DUMP_SEED = 264
+DUMP_SAMPLES = (2_000_000, 500_000, 500_000)   # scattered samples of the Y, Cb, Cr planes of the whole batch
+
+
+def dump_outputs(path: str, planes, npics: int, W: int, H: int, band, tag: str = ""):
+    """--dump-outputs: what the last step left in the output planes (`planes`: Y, Cb, Cr device
+    arrays of `npics` 4:2:0 pictures each), as float32 .npy files of about 50 MB in all: the first,
+    middle and last picture whole (`<y|u|v>_pictures`: [3, rows, columns], the rows of `band`) and a
+    fixed seeded sample of positions over every picture of the batch (`<y|u|v>_samples`)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    whole = sorted({0, npics // 2, npics - 1})
+    for k, name in enumerate("yuv"):
+        m = 16 if k == 0 else 8
+        rows, cols = m * H, m * W
+        r0, r1 = band[0] * m, band[1] * m
+        flat = planes[k].view(-1)[: npics * rows * cols]
+        pics = flat.view(npics, rows, cols)[whole, r0:r1].to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}_pictures{tag}.npy"), pics)
+        rng = np.random.default_rng(DUMP_SEED + k)
+        ns = DUMP_SAMPLES[k]
+        pos = (rng.integers(0, npics, ns) * rows + rng.integers(r0, r1, ns)) * cols + rng.integers(0, cols, ns)
+        got = flat[torch.from_numpy(np.sort(pos)).to(flat.device)].to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}_samples{tag}.npy"), got)
 
 
 def latency_chain(dec, L, cfg, refs, stream, n: int, verify: int):
@@ -341,7 +438,7 @@ def chain_run(args, rank: int, world: int, local: int, cs, rehearse: bool, nchai
             G["ev_ex"].append(ex)
 
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # two steps, then chain 0 of group 0 against the oracle's chain: its second picture read
         # the first one through the exchange, so the band (and the halo rows received) must equal
         # the oracle's whole-picture decode
@@ -400,6 +497,10 @@ def chain_run(args, rank: int, world: int, local: int, cs, rehearse: bool, nchai
     achieved = step_bytes / (kern[3] * 1e-3) / 1e9 if kern[3] > 0 else 0.0
     xin = groups[0]["xch"].bytes_in() * ng if world > 1 else 0
     xops = 0 if world == 1 else ng * xch_ops(groups[0]["xch"], bands, rank, halo, exchange)
+    if args.dump_outputs and band[1] > band[0] and args.steps + args.warmup > 0:
+        for g, G in enumerate(groups):                 # the set the last step wrote, this rank's band
+            dump_outputs(args.dump_outputs, G["sets"][(nstep[0] - 1) % 2], nk, W, H, band,
+                         (f"_group{g}" if ng > 1 else "") + (f"_rank{rank}" if world > 1 else ""))
     del groups, dec
     torch.cuda.empty_cache()
     # PMC traffic of this mode (tools/pmc.sh over a chain-mode run -> profiles/traffic_c<N>_chain.json)
@@ -414,7 +515,7 @@ def chain_run(args, rank: int, world: int, local: int, cs, rehearse: bool, nchai
     # the CPU path beside it (rank 0 at one GPU): the oracle port on a bounded sample of the same
     # pictures, 1 thread and a thread pool (a chain's picture costs the CPU what an independent one does)
     cpu = cpu_mt = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         done, el, ncpu = cpu_baseline(cfg, refs, args.cpu_seconds)
         cpu = {"value": done / el, "unit": "macroblocks/s", "cores": 1, "kind": "port",
                "sample": f"{ncpu} pictures of {CONFIG_NAMES[cfg_idx]} ({ncpu * nmb} MBs, {el:.1f} s) decoded by "
@@ -507,20 +608,17 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
 
     # inputs.  replicas: this rank's own pictures.  slices (weak scaling): every rank
     # holds the same world * nb pictures and reconstructs its band of slices of each.
-    if shard == "replicas":
-        pics = [synth.picture(L, cfg, i) for i in D.picture_share(rank, world, nb)]
-    else:
-        pics = [synth.picture(L, cfg, i) for i in range(world * nb)]
-    npics = len(pics)
+    # Generated and packed in chunks by worker threads (the generator is C and seeded per
+    # picture index, so the batch is the same bytes whatever the chunking).
+    index = list(D.picture_share(rank, world, nb)) if shard == "replicas" else list(range(world * nb))
+    npics = len(index)
+    check_idx = sorted({0, npics // 2, npics - 1}) if shard == "replicas" else [0]
+    chunks = packed_chunks(L, cfg, index, args.full)
     refs = synth.refpics(L, cfg)
-    rd = wr = 0
-    for p in pics:
-        r, w = synth.algo_bytes(L, p)
-        rd += r
-        wr += w
+    rd, wr = sum(c["rd"] for c in chunks), sum(c["wr"] for c in chunks)
     band = (0, H)
     if shard == "slices":
-        srow = pics[0].mbs["slice"].reshape(H, W)[:, 0]
+        srow = chunks[0]["host"]["mbs"]["slice"][: W * H].reshape(H, W)[:, 0]
         first = [0] + [r for r in range(1, H) if srow[r] != srow[r - 1]]
         bands = D.slice_bands(first, H, world)
         band = bands[rank]
@@ -563,14 +661,11 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     # before the batch and the library's scratch, shifting where every buffer lands in HBM
     pad_mb = int(os.environ.get("H264R_BENCH_PAD_MB", "0"))
     pad = torch.empty(pad_mb << 20, dtype=torch.uint8, device="cuda") if pad_mb > 0 else None
-    host = B.pack(pics, h264r.quant_flat())
-    db = B.to_device(host, npics, tabs[0].data_ptr())
-    # the batch is resident in HBM now: keep only what the checks below read (three
-    # pictures and the per-kernel algorithmic bytes), so a rank holds ~4 MB per picture once
-    kbytes_all = kernel_bytes(pics, nmb)
-    check_idx = sorted({0, npics // 2, npics - 1}) if shard == "replicas" else [0]
-    check_pics = {i: pics[i] for i in check_idx}
-    del host, pics
+    db = chunks_to_device(chunks, npics, tabs[0].data_ptr())
+    # the batch is resident in HBM now: keep only what --full's checks read (the per-kernel
+    # algorithmic bytes; the three checked pictures are generated again from their indices)
+    kbytes_all = [sum(c["kbytes"][i] for c in chunks) for i in range(3)] if args.full else None
+    del chunks
     stream = cs.cuda_stream
     comm = torch.cuda.Stream(device=local) if shard == "slices" else None
     stage = ([torch.zeros(max(b1 - b0 for b0, b1 in bands) * m * rb, dtype=torch.uint8, device="cuda")
@@ -614,7 +709,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     # batch vs the oracle (the largest offsets are checked too).  Slices: after
     # the exchange, the picture every rank received in E[2] vs the oracle's picture 0.
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         step()
         torch.cuda.synchronize()
         dec.check()
@@ -622,7 +717,8 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import _oracle as O
             verified = True
-            for i, p in check_pics.items():
+            for i in check_idx:
+                p = synth.picture(L, cfg, index[i])
                 want = O.decode(p, refs)
                 if shard == "slices":
                     got = [ring[2][k][: plane_rows[k] * row_bytes[k]].cpu().numpy().reshape(want[k].shape)
@@ -655,6 +751,9 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     kern = np.array(dec.last_timing()) if band[1] > band[0] else np.zeros(4)
     dec.set_timing(False)
     dt = D.max_over_ranks(dt, device="cpu" if rehearse else "cuda")
+    if args.dump_outputs and band[1] > band[0]:
+        dump_outputs(args.dump_outputs, [db.tensors[k] for k in ("out_y", "out_u", "out_v")], npics, W, H, band,
+                     f"_rank{rank}" if world > 1 else "")
 
     total_mbs = (world * nb if shard == "replicas" else npics) * nmb * args.steps
     value = total_mbs / dt
@@ -667,8 +766,10 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     # sequence on its stream, averaged over the timed steps)
     achieved = step_bytes / (kern[3] * 1e-3) / 1e9 if kern[3] > 0 else 0.0
     # per-kernel split of the same 8(d) bytes (kernel_bytes: R to the reconstructing kernel,
-    # W to deblocking; the parts add up to the path's bytes), over each kernel's own event time
-    kbytes = [int(k * (band[1] - band[0]) / H) for k in kbytes_all]
+    # W to deblocking; the parts add up to the path's bytes), over each kernel's own event time.
+    # This split, the PMC traffic, the copy peak, the CPU baselines and the latency chain below
+    # are --full's: a plain run reports the path's own figures only
+    kbytes = [int(k * (band[1] - band[0]) / H) for k in kbytes_all] if args.full else None
     # the library deblocks launches of fewer than H264R_DB2S_MAX (default 512) x 68 picture-MB-rows
     # with the split walk (k_deblock2y + k_deblock2c), larger ones with k_deblock2 (h264r_host.hip)
     prow = npics * (band[1] - band[0])
@@ -687,7 +788,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     tpath = args.traffic_json or os.path.join(ROOT, "profiles", "traffic.json")
     if not args.traffic_json and args.config != 3 and os.path.exists(os.path.join(ROOT, "profiles", f"traffic_c{args.config}.json")):
         tpath = os.path.join(ROOT, "profiles", f"traffic_c{args.config}.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         tj = json.load(open(tpath))
         if tj.get("survey_config", 3) == args.config:
             per = {k: v["traffic_bytes_per_mb"] for k, v in tj["kernels"].items()}
@@ -698,7 +799,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
             if all(vper.get(n) is not None for kn in kern_names for n in kn if n in vper):
                 kvalu = [sum(vper.get(n) or 0.0 for n in kn) for kn in kern_names]
     kernels = {}
-    for i, nme in enumerate(names):
+    for i, nme in enumerate(names if args.full else []):
         ach = kbytes[i] / (kern[i] * 1e-3) / 1e9 if kern[i] > 0 else 0.0
         kernels[nme] = {"ms": float(kern[i]), "algo_bytes": kbytes[i], "achieved": ach,
                         "frac": ach / HBM_PEAK_GBS, "traffic": ktraffic[i]}
@@ -714,7 +815,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
     # a measured copy-kernel peak beside the spec peak (device-to-device copy
     # of 1 GiB, read + write bytes over its HIP-event time, best of 5), outside the timed region
     copy_peak = None
-    if band[1] > band[0]:
+    if args.full and band[1] > band[0]:
         src = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
         dst = torch.empty_like(src)
         best = None
@@ -730,7 +831,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
         del src, dst
 
     cpu = cpu_mt = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         done, el, ncpu = cpu_baseline(cfg, refs, args.cpu_seconds)
         cpu = {"value": done / el, "unit": "macroblocks/s", "cores": 1, "kind": "port",
                "sample": f"{ncpu} pictures of the same {CONFIG_NAMES[args.config]} workload "
@@ -744,7 +845,7 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
                             f"oracle_decode_pictures, on {cpu_model()}"}
 
     latency = None
-    if rank == 0 and world == 1 and args.latency_pictures > 0 and shard == "replicas":
+    if args.full and rank == 0 and world == 1 and args.latency_pictures > 0 and shard == "replicas":
         ms, nl, lver = latency_chain(dec, L, cfg, refs, stream, args.latency_pictures,
                                      0 if args.no_verify else 3)
         latency = {"ms_per_picture": ms, "pictures": nl, "macroblocks_per_s": nmb / (ms * 1e-3),
@@ -774,7 +875,8 @@ def throughput_run(args, rank: int, world: int, local: int, cs, rehearse: bool, 
                          "path_frac_wall": value / world * step_bytes / max(mbs_rank, 1) / (HBM_PEAK_GBS * 1e9),
                          "read_frac": (rd / (kern[3] * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern[3] > 0 else 0.0,
                          "valu_floor_ms": (sum(k["valu_floor_ms"] for k in kernels.values())
-                                           if all("valu_floor_ms" in k for k in kernels.values()) else None),
+                                           if kernels and all("valu_floor_ms" in k for k in kernels.values())
+                                           else None),
                          "copy_peak_measured": copy_peak,
                          "frac_of_copy_peak": (achieved / copy_peak) if copy_peak else None,
                          "kernels": kernels},
@@ -800,6 +902,14 @@ def main() -> int:
                     help="GPUs = ranks; without WORLD_SIZE in the environment bench.py starts them itself")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: verify the output against the oracle before timing, the "
+                         "CPU baselines, the latency chain, the per-kernel roofline split with the PMC traffic "
+                         "and the measured copy peak, and at N > 1 the slice-sharded line and the one-GPU "
+                         "line of the same mode (a plain run sets up, warms up, times the steps and prints)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (three whole pictures and a "
+                         "seeded sample of the batch's output planes) as DIR/<name>.npy, float32")
     ap.add_argument("--config", type=int, default=None, choices=[2, 3, 4, 5],
                     help="SURVEY 8(d) workload (default: 3 at one GPU, 5 at N > 1)")
     ap.add_argument("--mode", choices=["throughput", "chain"], default=None,
@@ -847,7 +957,7 @@ def main() -> int:
     # N > 1 with no --mode: the headline workload as replicas (the value the scaling curve
     # compares with the one-GPU line), plus the slice-sharded dependent-chain run of config 5
     # beside it in the same JSON line (`slice_sharded`)
-    sliced = world > 1 and args.mode is None and not args.chain and not args.no_sliced
+    sliced = args.full and world > 1 and args.mode is None and not args.chain and not args.no_sliced
     if args.config is None:
         args.config = 5 if mode == "chain" else 3
 
@@ -887,9 +997,10 @@ def main() -> int:
         nch = args.chain or args.chains_per_gpu * world
         out = chain_run(args, rank, world, local, cs, rehearse, nch, args.config, args.exchange)
         out["distributed"] = ranks
-        if world > 1 and not args.no_n1:
+        if args.full and world > 1 and not args.no_n1:
             # the one-GPU line of the same mode and per-GPU load (weak scaling reference), on
             # rank 0 alone after the N-rank run; the other ranks wait at the barrier
+            args.dump_outputs = None                    # the N-rank run's outputs stay
             if rank == 0:
                 n1 = chain_run(args, 0, 1, local, cs, rehearse, nch // world, args.config, args.exchange)
                 out["same_mode_n1"] = {k: n1[k] for k in ("value", "ms_per_step", "verified_vs_oracle", "kernel_ms")}
@@ -909,6 +1020,7 @@ def main() -> int:
         # reference).  Reported beside the headline, which stays the replicas of config 3.
         torch.cuda.empty_cache()
         dist.barrier()
+        args.dump_outputs = None                        # the headline run's outputs stay
         nch = args.chains_per_gpu * world
         sl = chain_run(args, rank, world, local, cs, rehearse, nch, 5, args.exchange)
         if rank == 0:

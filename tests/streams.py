@@ -290,7 +290,15 @@ def read_capture_file(path: str) -> list[dict]:
     return pics
 
 
-def save_capture(path: str, pics: list[dict]) -> None:
+CAP_FILE_MAX = 1 << 20      # no committed fixture file is larger: a longer capture continues in part files
+
+
+def capture_part(path: str, k: int) -> str:
+    """Part k of a capture: <name>.cap.npz, then <name>.cap.1.npz, <name>.cap.2.npz, ..."""
+    return path if k == 0 else f"{path[:-len('.npz')]}.{k}.npz"
+
+
+def _save_capture_part(path: str, pics: list[dict]) -> None:
     arrs = {}
     for i, p in enumerate(pics):
         for k in ("mbs", "levels", "mv", "ref_idx", "slices", "pic", "quant"):
@@ -301,7 +309,35 @@ def save_capture(path: str, pics: list[dict]) -> None:
     np.savez_compressed(path, n=np.array([len(pics)]), **arrs)
 
 
+def save_capture(path: str, pics: list[dict]) -> None:
+    """The pictures in decoding order over as many part files as keep each within CAP_FILE_MAX
+    (a part that comes out larger is halved, down to one picture per part)."""
+    parts = [pics]
+    while True:
+        for k, part in enumerate(parts):
+            _save_capture_part(capture_part(path, k), part)
+        big = [k for k, part in enumerate(parts)
+               if len(part) > 1 and os.path.getsize(capture_part(path, k)) > CAP_FILE_MAX]
+        if not big:
+            break
+        k = big[0]
+        half = len(parts[k]) // 2
+        parts[k: k + 1] = [parts[k][:half], parts[k][half:]]
+    k = len(parts)
+    while os.path.exists(capture_part(path, k)):       # parts of an earlier, longer capture
+        os.remove(capture_part(path, k))
+        k += 1
+
+
 def load_capture(path: str) -> list[dict]:
+    pics, k = _load_capture_part(path), 1
+    while os.path.exists(capture_part(path, k)):
+        pics += _load_capture_part(capture_part(path, k))
+        k += 1
+    return pics
+
+
+def _load_capture_part(path: str) -> list[dict]:
     z = np.load(path, allow_pickle=False)
     dt = {"mbs": A.MB_DTYPE, "slices": A.SLICE_DTYPE, "pic": A.PIC_DTYPE, "quant": A.QUANT_DTYPE}
     pics = []

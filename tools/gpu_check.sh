@@ -19,13 +19,13 @@ if has tests; then run tests
 if has smoke; then run smoke
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log; fi
 if has bench; then run bench
-  timeout -k 10 400 python bench.py > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 400 $O/bench_c3.json; echo; fi
+  timeout -k 10 400 python bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err; tail -c 400 $O/bench_c3.json; echo; fi
 if has chain5; then run chain5
-  timeout -k 10 400 python bench.py --mode chain --config 5 --steps 10 > $O/chain_c5.json 2> $O/chain_c5.err; tail -c 300 $O/chain_c5.json; echo; fi
+  timeout -k 10 400 python bench.py --full --mode chain --config 5 --steps 10 > $O/chain_c5.json 2> $O/chain_c5.err; tail -c 300 $O/chain_c5.json; echo; fi
 if has chain4; then run chain4
-  timeout -k 10 400 python bench.py --mode chain --config 4 --steps 10 > $O/chain_c4.json 2> $O/chain_c4.err; tail -c 300 $O/chain_c4.json; echo; fi
+  timeout -k 10 400 python bench.py --full --mode chain --config 4 --steps 10 > $O/chain_c4.json 2> $O/chain_c4.err; tail -c 300 $O/chain_c4.json; echo; fi
 for c in 2 4 5; do if has c$c; then run c$c
-  timeout -k 10 400 python bench.py --config $c --no-cpu --latency-pictures 0 > $O/bench_c$c.json 2> $O/bench_c$c.err; tail -c 300 $O/bench_c$c.json; echo; fi; done
+  timeout -k 10 400 python bench.py --full --config $c --no-cpu --latency-pictures 0 > $O/bench_c$c.json 2> $O/bench_c$c.err; tail -c 300 $O/bench_c$c.json; echo; fi; done
 if has prof; then run prof
   cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof -o run -- \
     python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu --latency-pictures 0 > $GRAFT_REPO_ROOT/$O/prof_bench.json 2> $GRAFT_REPO_ROOT/$O/prof.err
