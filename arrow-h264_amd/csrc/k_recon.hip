@@ -114,10 +114,13 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
             const bool valid = a < aend;
             const int aa = valid ? a : aend - 1;
             const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
-            const uint2 m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, pre.q.slice, 1);
+            // P pictures: the records without the list-1 motion words and with the one-list comparison
+            const bool one = (H264R_INTER_FAST & 2) && inter4_one_list(pre, nb);
+            uint2 m1 = inter4_no_list();
+            if (!one) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, pre.q.slice, 1);
             if (!(H264R_INTER_DIAG & 32))
                 dbinfo_block(b, g, pic, aa, valid, lane & 15, S, T, pre.q, m0, m1, slice_hdr(slices, S, pre.q.slice), nb,
-                             dbinfo + (size_t)pic * g.nmb);
+                             dbinfo + (size_t)pic * g.nmb, one);
         }
         int ln = lane;
         asm volatile("" : "+v"(ln));

@@ -58,6 +58,18 @@ DEV int bs_compare(const MotionRef& p, const MotionRef& q, int mvlim)   // deblo
     return 1;
 }
 
+// bs_compare when list 1 is unused on both sides (ref[1] == -1, its mv zero) and at least one side
+// has a list-0 reference: "another reference, or an mv component apart by the limit".  With p1 ==
+// q1 == -1 bs_compare's first test is p0 == q0 (the crossed form needs p0 == -1 == q0, the same);
+// different references return 1.  Equal ones are not -1 here, so p0 != p1 and the result is
+// cmp_mv(0, 0) | cmp_mv(1, 1), whose second term compares two zero vectors.  (With p0 == q0 == -1
+// bs_compare takes its four-way form, which also weighs each list-0 mv against zero: the caller
+// keeps such blocks away.)
+DEV int bs_compare_one(const MotionRef& p, const MotionRef& q, int mvlim)
+{
+    return (int)(p.ref[0] != q.ref[0]) | cmp_mv(p, 0, q, 0, mvlim);
+}
+
 DEV int special_slice(int t) { return t == H264R_SLICE_SP || t == H264R_SLICE_SI; }
 
 // Per-MB deblocking record, produced by k_inter for every MB (fully parallel) so

@@ -34,6 +34,12 @@
 #ifndef H264R_INTER_DIAG
 #define H264R_INTER_DIAG 0
 #endif
+// H264R_INTER_FAST: the two shortcuts of k_inter4r, each wave-uniform with today's code as the other
+// branch, so either can be A/B'd alone (make EXTRA=-DH264R_INTER_FAST=<bits>): 1 the residual and
+// the construction on packed 16-bit pairs (inter4_mbs<false>), 2 one-list deblocking records
+#ifndef H264R_INTER_FAST
+#define H264R_INTER_FAST 3
+#endif
 
 namespace h264r {
 
@@ -170,6 +176,45 @@ DEV s16x2 splat16(short v) { return (s16x2){v, v}; }
 DEV s16x2 pk_max(s16x2 a, s16x2 b) { return __builtin_elementwise_max(a, b); }
 DEV s16x2 pk_min(s16x2 a, s16x2 b) { return __builtin_elementwise_min(a, b); }
 DEV s16x2 pk_clip255(s16x2 a) { return pk_min(pk_max(a, splat16(0)), splat16(255)); }
+// {a's low half, b's low half} / {a's high half, b's high half}
+DEV s16x2 pk_lo(uint32_t a, uint32_t b) { return as_s16x2(__builtin_amdgcn_perm(b, a, 0x05040100u)); }
+DEV s16x2 pk_hi(uint32_t a, uint32_t b) { return as_s16x2(__builtin_amdgcn_perm(b, a, 0x07060302u)); }
+// {a, b} saturated to 16 bits each
+DEV s16x2 pk_sat(int a, int b) { return __builtin_bit_cast(s16x2, __builtin_amdgcn_cvt_pk_i16(a, b)); }
+// idct4 (device_common.h) on both halves
+DEV void idct4_pk(s16x2& a, s16x2& b, s16x2& c, s16x2& d)
+{
+    const s16x2 e0 = a + c, e1 = a - c, e2 = (b >> splat16(1)) - d, e3 = b + (d >> splat16(1));
+    a = e0 + e3; b = e1 + e2; c = e1 - e2; d = e0 - e3;
+}
+// dq4 (device_common.h) + 2^27 as an unsigned value, for every 32-bit product: the sign bit flipped
+// is + 2^31 before a logical shift.  The low 16 bits are dq4's, and |dq4| = |u - 2^27| is one
+// v_sad_u32 (no wrap: |dq4| <= 2^27, so 16 of them sum below 2^32).
+constexpr uint32_t DQ4_BIAS = 1u << 27;
+DEV uint32_t dq4_biased(int lev, int scale, int per) { return ((uint32_t)(lev * scale) * (1u << per) + 0x80000008u) >> 4; }
+DEV uint32_t abs_acc_biased(uint32_t u, uint32_t acc)
+{
+    uint32_t r;
+    asm("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(u), "s"(DQ4_BIAS), "v"(acc));
+    return r;
+}
+// The packed 16-bit inverse transforms below are exact when the block's 16 dequantised coefficients
+// have sum |d| <= PK_RES_MAX.  Each 1-D pass (idct4) forms its intermediates and outputs from its
+// four inputs with weights of magnitude <= 1 (|x >> 1| <= |x|), so after the first pass an entry is
+// at most its line's sum |d|, and every intermediate and output of the second pass at most the sum
+// of those, the block's sum |d|.  The rounding is folded in as +32 on d[0][0] before the first pass:
+// the DC takes only the unshifted e0 / e1 = d0 +- d2 paths, so every output gains exactly 32, as
+// (x + 32) >> 6 asks.  With it no value leaves [-32732, 32732], inside int16.  The sum is taken on
+// the 32-bit values (a coefficient past int16 fails it like a large sum does).
+constexpr uint32_t PK_RES_MAX = 32700;
+// Construction of one row of four samples: prediction bytes + residual pairs {0, 1}, {2, 3}
+// (saturated to 16 bits, pk_sat: the clip to 0..255 decides the same), clipped.
+DEV uint32_t construct4(uint32_t pred, s16x2 r01, s16x2 r23)
+{
+    const s16x2 p01 = as_s16x2(__builtin_amdgcn_perm(0, pred, 0x0c010c00u)), p23 = as_s16x2(__builtin_amdgcn_perm(0, pred, 0x0c030c02u));
+    const s16x2 s01 = pk_clip255(__builtin_elementwise_add_sat(p01, r01)), s23 = pk_clip255(__builtin_elementwise_add_sat(p23, r23));
+    return __builtin_amdgcn_perm(as_u32(s23), as_u32(s01), 0x06040200u);
+}
 // (p[k], p[k+1]) of the 9 row samples held as bytes in r0 = p0..p3, r1 = p4..p7, r2 = p8
 template <int K>
 DEV s16x2 pair_at(uint32_t r0, uint32_t r1, uint32_t r2)
@@ -479,85 +524,120 @@ DEV int mb_qp(const h264r_mb& m, int pl)
     return pl == 0 ? (int)(int8_t)(w0 >> 24) : (int)(int8_t)(w1 >> (8 * (pl - 1)));
 }
 
+// A list without motion as motion_word would give it (ref_idx -1, no slot, zero mv), without the
+// table read.
+DEV uint2 inter4_no_list() { return make_uint2(0, 0xFFFFu); }
+// True when no lane's block, left block or upper block has list-1 motion: every ref_idx of list 1 is
+// negative and every mv word of it zero (P pictures, and the waves of a B picture that predict from
+// list 0 alone).  The list-1 motion words of those blocks are then all inter4_no_list().
+DEV bool inter4_one_list(const Inter4Pre& pre, const DbNb& nb)
+{
+    const bool used = (pre.ri[1] & nb.lri[1] & nb.uri[1]) >= 0 || (pre.mv[1] | nb.lmv[1] | nb.umv[1]) != 0;
+    return !__any(used);
+}
+
+// The record of dbinfo_block once the motion of the block (mq), of its left (ml) and of its upper
+// neighbour (mu) is resolved.  ONE: the wave compares one list (bs_compare_one).
+template <bool ONE>
+DEV void dbinfo_records(const h264r_mb& q, const h264r_mb& L, const h264r_mb& U, const MotionRef& mq, const MotionRef& ml,
+                        const MotionRef& mu, int blk, int hasL, int hasU, uint32_t qsh0, int l_type, int u_type, int fld,
+                        const DbTables& T, DbInfo* __restrict__ out)
+{
+    const int bx = blk & 3, by = blk >> 2;
+    const int q_type = qsh0 & 255, idc = (qsh0 >> 8) & 255;
+    const int offa = (int8_t)((qsh0 >> 16) & 255), offb = (int8_t)(qsh0 >> 24);
+    const int mvlim = fld ? 2 : 4;
+    const int q_intra = mb_is_intra(q);
+    const int fl = idc == 0 ? hasL : (idc == 2 && hasL && L.slice == q.slice);
+    const int ft = idc == 0 ? hasU : (idc == 2 && hasU && U.slice == q.slice);
+    const int t8 = (q.flags & H264R_MBF_T8x8) != 0;
+    const int pskip = q_type == H264R_SLICE_P && q.mb_type == H264R_P_SKIP;
+    const int special_q = special_slice(q_type);
+#pragma unroll
+    for (int hor = 0; hor < 2; ++hor) {
+        const int e = hor ? by : bx, s = hor ? bx : by;
+        const int en = idc != 1 && (e == 0 ? (hor ? ft : fl) : ((e & 1) ? !t8 : 1));
+        int v = 0;
+        if (en) {
+            // MB P of the edge: the left / upper MB for edge 0, else this MB
+            const int p_flags = e == 0 ? (hor ? U.flags : L.flags) : q.flags;
+            const int p_cbp = e == 0 ? (hor ? U.cbp_blks : L.cbp_blks) : q.cbp_blks;
+            const int special = special_q || (e == 0 && special_slice(hor ? u_type : l_type));
+            const int intra = q_intra || (p_flags & H264R_MBF_INTRA) != 0;
+            const int blkQ = 4 * by + bx;
+            const int blkP = hor ? (e == 0 ? 12 + bx : blkQ - 4) : (e == 0 ? blkQ + 3 : blkQ - 1);
+            const int coded = ((q.cbp_blks >> blkQ) & 1) || ((p_cbp >> blkP) & 1);
+            const int same_part = e > 0 && (q.mb_type == H264R_P_16x16 ||
+                                            q.mb_type == (hor ? H264R_P_8x16 : H264R_P_16x8));
+            if (!hor) {
+                if (special) v = e == 0 ? 4 : 3;
+                else if (e > 0 && pskip) v = 0;
+                else if (e == 0 && intra) v = 4;
+                else if (intra) v = 3;
+                else if (coded) v = 2;
+                else if (same_part) v = 0;
+                else v = ONE ? bs_compare_one(mq, ml, mvlim) : bs_compare(mq, ml, mvlim);
+            } else {
+                if (e == 0 && !fld && (special || intra)) v = 4;
+                else if (special || intra) v = 3;
+                else if (e > 0 && pskip) v = 0;
+                else if (coded) v = 2;
+                else if (same_part) v = 0;
+                else v = ONE ? bs_compare_one(mq, mu, mvlim) : bs_compare(mq, mu, mvlim);
+            }
+        }
+        out->bs[hor * 16 + e * 4 + s] = (uint8_t)v;
+    }
+    if (blk < 9) {                                              // edge parameters
+        const int pl = blk / 3, which = blk - pl * 3;
+        // QP of plane pl from the record's dwords 0 / 1 (a select between the byte fields
+        // became a select of their addresses: the record went to memory, promoted to LDS)
+        const h264r_mb& P = which == 0 ? L : (which == 1 ? U : q);
+        const int qp = mb_qp(P, pl), qq = mb_qp(q, pl);
+        out->par[blk] = edge_word(qp, qq, offa, offb, T.ab, T.tc0);
+    }
+}
+
 // The deblocking record of one MB's 4x4 block (Deblock::strength deblock.cc:78-289,
 // edge parameters :469-480): the block's left edge (vertical edge bx, segment by) and top
 // edge (horizontal edge by, segment bx), and for blk < 9 one alpha/beta/tc0 word.  Inside
 // k_inter4r, before the group's reconstruction.
+// `one` (wave-uniform, inter4_one_list): no list-1 motion in reach of any lane; m1 is then
+// inter4_no_list().
 DEV void dbinfo_block(const h264r_batch& b, const Geom& g, int pic, int aa, bool valid, int blk, const Inter4Lds& S, const DbTables& T,
-                      const h264r_mb& q, uint2 m0, uint2 m1, uint2 qsh, const DbNb& nb, DbInfo* __restrict__ dbout)
+                      const h264r_mb& q, uint2 m0, uint2 m1, uint2 qsh, const DbNb& nb, DbInfo* __restrict__ dbout, bool one)
 {
     const int bx = blk & 3, by = blk >> 2;
     const int mbx = aa % g.wmb, mby = aa / g.wmb;
     const h264r_slice* slices = b.slices + (size_t)pic * b.slice_stride;
     const int hasL = mbx > 0, hasU = mby > 0;
-    const int q_type = qsh.x & 255, idc = (qsh.x >> 8) & 255;
-    const int offa = (int8_t)((qsh.x >> 16) & 255), offb = (int8_t)(qsh.x >> 24);
     const h264r_mb& L = nb.L;
     const h264r_mb& U = nb.U;
     // the neighbour block belongs to this MB or to the left / upper one (its slice resolves it)
     const int lsl = bx > 0 ? q.slice : L.slice, usl = by > 0 ? q.slice : U.slice;
-    const uint2 l0 = motion_word(nb.lmv[0], nb.lri[0], slices, S, lsl, 0), l1 = motion_word(nb.lmv[1], nb.lri[1], slices, S, lsl, 1);
-    const uint2 u0 = motion_word(nb.umv[0], nb.uri[0], slices, S, usl, 0), u1 = motion_word(nb.umv[1], nb.uri[1], slices, S, usl, 1);
+    const uint2 l0 = motion_word(nb.lmv[0], nb.lri[0], slices, S, lsl, 0), u0 = motion_word(nb.umv[0], nb.uri[0], slices, S, usl, 0);
+    uint2 l1 = inter4_no_list(), u1 = l1;
+    if (!one) {
+        l1 = motion_word(nb.lmv[1], nb.lri[1], slices, S, lsl, 1);
+        u1 = motion_word(nb.umv[1], nb.uri[1], slices, S, usl, 1);
+    }
     const int l_type = slice_type_of(slices, S, L.slice), u_type = slice_type_of(slices, S, U.slice);
     // field pictures: mvlimit 2 (deblock.cc:86,164) and no bS 4 across horizontal MB edges
     // (cond_bS4 = !field || vertical, deblock.cc:103-107,184-189)
     const int fld = (int)__builtin_amdgcn_readfirstlane(ld_const(&b.pics[pic].structure)) != H264R_FRAME;
-    const int mvlim = fld ? 2 : 4;
     // ---- deblocking record (Deblock::strength deblock.cc:78-289): this lane's
     // left edge (vertical edge bx, segment by) and top edge (horizontal edge by,
     // segment bx)
     if (valid) {
-        const int fl = idc == 0 ? hasL : (idc == 2 && hasL && L.slice == q.slice);
-        const int ft = idc == 0 ? hasU : (idc == 2 && hasU && U.slice == q.slice);
-        const int t8 = (q.flags & H264R_MBF_T8x8) != 0;
-        const MotionRef mq = motion_of(m0, m1);
-        const int q_intra = mb_is_intra(q);
-        const int pskip = q_type == H264R_SLICE_P && q.mb_type == H264R_P_SKIP;
-        const int special_q = special_slice(q_type);
+        const MotionRef mq = motion_of(m0, m1), ml = motion_of(l0, l1), mu = motion_of(u0, u1);
+        // bs_compare_one also needs a list-0 reference on one side of every edge it is asked about.
+        // Only edges between two inter MBs reach the comparison, so an inter MB's block without one
+        // (no conforming stream has it: ref_idx out of range, or an empty RefPicList entry) sends
+        // the wave to bs_compare.
+        if (one) one = !__any(!mb_is_intra(q) && mq.ref[0] < 0 && (ml.ref[0] < 0 || mu.ref[0] < 0));
         DbInfo* out = dbout + aa;
-#pragma unroll
-        for (int hor = 0; hor < 2; ++hor) {
-            const int e = hor ? by : bx, s = hor ? bx : by;
-            const int en = idc != 1 && (e == 0 ? (hor ? ft : fl) : ((e & 1) ? !t8 : 1));
-            int v = 0;
-            if (en) {
-                // MB P of the edge: the left / upper MB for edge 0, else this MB
-                const int p_flags = e == 0 ? (hor ? U.flags : L.flags) : q.flags;
-                const int p_cbp = e == 0 ? (hor ? U.cbp_blks : L.cbp_blks) : q.cbp_blks;
-                const int special = special_q || (e == 0 && special_slice(hor ? u_type : l_type));
-                const int intra = q_intra || (p_flags & H264R_MBF_INTRA) != 0;
-                const int blkQ = 4 * by + bx;
-                const int blkP = hor ? (e == 0 ? 12 + bx : blkQ - 4) : (e == 0 ? blkQ + 3 : blkQ - 1);
-                const int coded = ((q.cbp_blks >> blkQ) & 1) || ((p_cbp >> blkP) & 1);
-                const int same_part = e > 0 && (q.mb_type == H264R_P_16x16 ||
-                                                q.mb_type == (hor ? H264R_P_8x16 : H264R_P_16x8));
-                if (!hor) {
-                    if (special) v = e == 0 ? 4 : 3;
-                    else if (e > 0 && pskip) v = 0;
-                    else if (e == 0 && intra) v = 4;
-                    else if (intra) v = 3;
-                    else if (coded) v = 2;
-                    else if (same_part) v = 0;
-                    else v = bs_compare(mq, motion_of(l0, l1), mvlim);
-                } else {
-                    if (e == 0 && !fld && (special || intra)) v = 4;
-                    else if (special || intra) v = 3;
-                    else if (e > 0 && pskip) v = 0;
-                    else if (coded) v = 2;
-                    else if (same_part) v = 0;
-                    else v = bs_compare(mq, motion_of(u0, u1), mvlim);
-                }
-            }
-            out->bs[hor * 16 + e * 4 + s] = (uint8_t)v;
-        }
-        if (blk < 9) {                                              // edge parameters
-            const int pl = blk / 3, which = blk - pl * 3;
-            // QP of plane pl from the record's dwords 0 / 1 (a select between the byte fields
-            // became a select of their addresses: the record went to memory, promoted to LDS)
-            const h264r_mb& P = which == 0 ? L : (which == 1 ? U : q);
-            const int qp = mb_qp(P, pl), qq = mb_qp(q, pl);
-            out->par[blk] = edge_word(qp, qq, offa, offb, T.ab, T.tc0);
-        }
+        if (one) dbinfo_records<true>(q, L, U, mq, ml, mu, blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+        else dbinfo_records<false>(q, L, U, mq, ml, mu, blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
     }
 }
 
@@ -900,17 +980,24 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
             }
             return;
         }
-        // ---- luma residual (transform.cc:1058-1073)
-        int res[4][4];
+        // ---- luma residual (transform.cc:1058-1073): rp[i][h] = {row i's columns 2h, 2h + 1} as a
+        // 16-bit pair, what the construction takes (construct4)
+        s16x2 rp[4][2];
     #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) rp[i][0] = rp[i][1] = splat16(0);
+        // the 32-bit paths' result, saturated (pk_sat)
+        auto pack_res = [&](const int (&res)[4][4]) {
     #pragma unroll
-            for (int c = 0; c < 4; ++c) res[i][c] = 0;
+            for (int i = 0; i < 4; ++i) {
+                rp[i][0] = pk_sat(res[i][0], res[i][1]);
+                rp[i][1] = pk_sat(res[i][2], res[i][3]);
+            }
+        };
         const bool byp = (q.flags & H264R_MBF_BYPASS) != 0;
 #if H264R_INTER_DIAG & 64
         // diagnostic build (wrong output): the luma levels loaded, not transformed
-        res[0][0] = (int)(lev[0].x ^ lev[0].y ^ lev[0].z ^ lev[0].w ^ lev[1].x ^ lev[1].y ^ lev[1].z ^ lev[1].w ^
-                          lsc[0].x ^ lsc[1].y) & 3;
+        rp[0][0].x = (short)((lev[0].x ^ lev[0].y ^ lev[0].z ^ lev[0].w ^ lev[1].x ^ lev[1].y ^ lev[1].z ^ lev[1].w ^
+                              lsc[0].x ^ lsc[1].y) & 3);
 #endif
         if (!(H264R_INTER_DIAG & (16 | 64)) && __any(cbpl != 0)) {
             const int per = qpl / 6;
@@ -918,18 +1005,27 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
             // lanes of a wave mix 4x4 and 8x8 MBs, and a select per value (not a branch) keeps
             // the 16 values free of exec-mask work
             const int drnd = t8 ? 32 : 8, dsh = t8 ? 6 : 4;
+            auto level_at = [&](int i, int c) {
+                const uint4 lw = lev[i >> 1];
+                return sel16((i & 1) ? lw.z : lw.x, (i & 1) ? lw.w : lw.y, c);
+            };
+            auto scale_at = [&](int i, int c) {
+                const uint4 sw = lsc[i >> 1];
+                return sel16((i & 1) ? sw.z : sw.x, (i & 1) ? sw.w : sw.y, c);
+            };
+            // (each branch below dequantises for itself: the lossless one takes the levels, the 4x4
+            // one a biased form its range test reads)
             int d[4][4];
+            auto dequant = [&]() {
     #pragma unroll
-            for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < 4; ++i)
     #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const uint4 lw = lev[i >> 1], sw = lsc[i >> 1];
-                    const uint32_t lo_ = (i & 1) ? lw.z : lw.x, hi_ = (i & 1) ? lw.w : lw.y;
-                    const uint32_t slo = (i & 1) ? sw.z : sw.x, shi = (i & 1) ? sw.w : sw.y;
-                    const int lvv = sel16(lo_, hi_, c), scv = sel16(slo, shi, c);
-                    const int dqv = ((lvv * scv) * (1 << per) + drnd) >> dsh;
-                    d[i][c] = byp ? lvv : dqv;
-                }
+                    for (int c = 0; c < 4; ++c) {
+                        const int lvv = level_at(i, c), scv = scale_at(i, c);
+                        const int dqv = ((lvv * scv) * (1 << per) + drnd) >> dsh;
+                        d[i][c] = byp ? lvv : dqv;
+                    }
+            };
             // lossless MBs (TransformBypassModeFlag): the levels are the residual, DPCM'd in
             // place down the columns / along the rows when the block's Intra4x4PredMode /
             // Intra8x8PredMode is vertical / horizontal (bypass_4x4 / bypass_8x8
@@ -937,6 +1033,7 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
             // for inter MBs too: whatever the parser's mb_t slot holds).  The flag is
             // uniform over an MB's 16 lanes, so the cross-lane carries stay inside the branch.
             if (byp) {
+                dequant();
                 const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
                 const uint64_t ipw = (uint64_t)qw[5] | ((uint64_t)qw[6] << 32);
                 const int bk = t8 ? b8 : (by >> 1) * 8 + (bx >> 1) * 4 + (by & 1) * 2 + (bx & 1);
@@ -963,25 +1060,71 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
     #pragma unroll
                     for (int c = 0; c < 4; ++c) d[i][c] += (t8 && horz && (bx & 1)) ? left : 0;
                 }
-    #pragma unroll
-                for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) res[i][c] = d[i][c];
+                pack_res(d);
             } else
             if (!__any(t8 != 0)) {
-                // 4x4: rows then columns, all in-lane
+                // 4x4, all in-lane.  On 16-bit pairs when every lane's block passes PK_RES_MAX (real
+                // content does): rows 0, 1 and rows 2, 3 as the halves of two transforms, a 2x2
+                // transpose of the pairs, then columns {0, 1} and {2, 3}
+                bool pk = (H264R_INTER_FAST & 1) != 0;
+                uint32_t u[4][4];
+                if (pk) {
+                    uint32_t gs = 0;
     #pragma unroll
-                for (int i = 0; i < 4; ++i) idct4_inplace(d[i][0], d[i][1], d[i][2], d[i][3]);
+                    for (int i = 0; i < 4; ++i)
     #pragma unroll
-                for (int c = 0; c < 4; ++c) idct4_inplace(d[0][c], d[1][c], d[2][c], d[3][c]);
+                        for (int c = 0; c < 4; ++c) {
+                            u[i][c] = dq4_biased(level_at(i, c), scale_at(i, c), per);
+                            gs = abs_acc_biased(u[i][c], gs);
+                        }
+                    pk = !__any(gs > PK_RES_MAX);
+                }
+                if (pk) {
+                    s16x2 A[4], B[4];
     #pragma unroll
-                for (int i = 0; i < 4; ++i)
+                    for (int c = 0; c < 4; ++c) {
+                        A[c] = pk_lo(u[0][c], u[1][c]);
+                        B[c] = pk_lo(u[2][c], u[3][c]);
+                    }
+                    A[0] += (s16x2){32, 0};
+                    idct4_pk(A[0], A[1], A[2], A[3]);
+                    idct4_pk(B[0], B[1], B[2], B[3]);
     #pragma unroll
-                    for (int c = 0; c < 4; ++c) res[i][c] = (d[i][c] + 32) >> 6;
+                    for (int h = 0; h < 2; ++h) {
+                        s16x2 x0 = pk_lo(as_u32(A[2 * h]), as_u32(A[2 * h + 1])), x1 = pk_hi(as_u32(A[2 * h]), as_u32(A[2 * h + 1]));
+                        s16x2 x2 = pk_lo(as_u32(B[2 * h]), as_u32(B[2 * h + 1])), x3 = pk_hi(as_u32(B[2 * h]), as_u32(B[2 * h + 1]));
+                        idct4_pk(x0, x1, x2, x3);
+                        rp[0][h] = x0 >> splat16(6); rp[1][h] = x1 >> splat16(6);
+                        rp[2][h] = x2 >> splat16(6); rp[3][h] = x3 >> splat16(6);
+                    }
+                } else {
+                    // rows then columns, 32-bit (the biased values are the dequantised ones + 2^27,
+                    // exactly: taken back, not computed again, so that the range test keeps its
+                    // own shift-and-add)
+                    if (H264R_INTER_FAST & 1) {
+    #pragma unroll
+                        for (int i = 0; i < 4; ++i)
+    #pragma unroll
+                            for (int c = 0; c < 4; ++c) d[i][c] = (int)(u[i][c] - DQ4_BIAS);
+                    } else {
+                        dequant();
+                    }
+    #pragma unroll
+                    for (int i = 0; i < 4; ++i) idct4_inplace(d[i][0], d[i][1], d[i][2], d[i][3]);
+    #pragma unroll
+                    for (int c = 0; c < 4; ++c) idct4_inplace(d[0][c], d[1][c], d[2][c], d[3][c]);
+                    int res[4][4];
+    #pragma unroll
+                    for (int i = 0; i < 4; ++i)
+    #pragma unroll
+                        for (int c = 0; c < 4; ++c) res[i][c] = (d[i][c] + 32) >> 6;
+                    pack_res(res);
+                }
             } else {
                 // 8x8 (only t8 MBs reach here with d != 0 for their lanes; 4x4 MBs of the same
                 // wave take the in-lane path below).  Rows: my 4 + the 4 of lane ^ 1.
-                int e4[4][4];
+                dequant();
+                int e4[4][4], res[4][4];
     #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     int in[8], outv[8];
@@ -1021,6 +1164,7 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
                 for (int i = 0; i < 4; ++i)
     #pragma unroll
                     for (int c = 0; c < 4; ++c) res[i][c] = ((t8 ? res[i][c] : d[i][c]) + 32) >> 6;
+                pack_res(res);
             }
         }
         // ---- construction + store, luma
@@ -1028,89 +1172,145 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
         {   // diagnostic build (wrong output): one 16-byte store per lane, an MB's 16 lanes contiguous
             uint32_t wv4[4];
     #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uint32_t wv = 0;
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) wv |= (uint32_t)clip255((int)((predY[i] >> (8 * c)) & 255) + res[i][c]) << (8 * c);
-                wv4[i] = wv;
-            }
+            for (int i = 0; i < 4; ++i) wv4[i] = construct4(predY[i], rp[i][0], rp[i][1]);
             *reinterpret_cast<uint4*>(rmb + blk * 16) = make_uint4(wv4[0], wv4[1], wv4[2], wv4[3]);
         }
 #else
     #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            uint32_t wv = 0;
-    #pragma unroll
-            for (int c = 0; c < 4; ++c) wv |= (uint32_t)clip255((int)((predY[i] >> (8 * c)) & 255) + res[i][c]) << (8 * c);
-            *reinterpret_cast<uint32_t*>(ydst + i * 16) = wv;
-        }
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<uint32_t*>(ydst + i * 16) = construct4(predY[i], rp[i][0], rp[i][1]);
 #endif
 
         // ---- chroma residual (transform.cc:1081-1091, DC :875-889): chroma block cb is
         // spread over lanes {blk, ^1, ^4, ^5}; my quadrant rows cr.., cols cc..
-    #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-            int rc[2][2] = {{0, 0}, {0, 0}};
+        // rcp[pl][r] = {row r's two samples of plane pl} as a 16-bit pair
+        s16x2 rcp[2][2] = {{splat16(0), splat16(0)}, {splat16(0), splat16(0)}};
 #if H264R_INTER_DIAG & 128
-            // diagnostic build (wrong output): the chroma levels loaded, not transformed
-            rc[0][0] = (int)(clev[pl][0] ^ clev[pl][1] ^ csc[pl][0] ^ csc[pl][1] ^ cdc[pl].x ^ cdc[pl].y ^ (uint32_t)cdcs[pl]) & 3;
+        // diagnostic build (wrong output): the chroma levels loaded, not transformed
+    #pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+            rcp[pl][0].x = (short)((clev[pl][0] ^ clev[pl][1] ^ csc[pl][0] ^ csc[pl][1] ^ cdc[pl].x ^ cdc[pl].y ^ (uint32_t)cdcs[pl]) & 3);
 #endif
-            if (!(H264R_INTER_DIAG & (16 | 128)) && __any(cbpc != 0)) {
+        if (!(H264R_INTER_DIAG & (16 | 128)) && __any(cbpc != 0)) {
+            const bool dcl_lane = cr == 0 && cc == 0;
+            // k: the dequantised coefficients + DQ4_BIAS (dq4_biased), the scaled DC among them
+            uint32_t k[2][2][2];
+            int dcl[2];
+    #pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
                 const int qpc = q.qp_scaled[1 + pl], per = qpc / 6;
-                int k[2][2], raw[2][2];
     #pragma unroll
                 for (int r = 0; r < 2; ++r)
     #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        raw[r][c] = (int16_t)(clev[pl][r] >> (16 * c));
-                        k[r][c] = dq4(raw[r][c], (int16_t)(csc[pl][r] >> (16 * c)), per);
-                    }
+                    for (int c = 0; c < 2; ++c)
+                        k[pl][r][c] = dq4_biased((int16_t)(clev[pl][r] >> (16 * c)), (int16_t)(csc[pl][r] >> (16 * c)), per);
                 const int c00 = (int16_t)(cdc[pl].x & 0xFFFF), c01 = (int16_t)(cdc[pl].x >> 16);
                 const int c10 = (int16_t)(cdc[pl].y & 0xFFFF), c11 = (int16_t)(cdc[pl].y >> 16);
                 const int e00 = c00 + c01, e01 = c00 - c01, e10 = c10 + c11, e11 = c10 - c11;
                 // f = (e00 or e01) +/- (e10 or e11) by cb's bits: arithmetic, not a branch tree
                 const int ea = (cb & 1) ? e01 : e00, eb = (cb & 1) ? e11 : e10;
                 const int f = ea + (eb ^ -(cb >> 1)) + (cb >> 1);
-                if (cr == 0 && cc == 0) k[0][0] = cbpc ? ((f * cdcs[pl]) * (1 << per)) >> 5 : 0;
+                if (dcl_lane) k[pl][0][0] = (uint32_t)(cbpc ? ((f * cdcs[pl]) * (1 << per)) >> 5 : 0) + DQ4_BIAS;
+                dcl[pl] = cb == 0 ? c00 : cb == 1 ? c01 : cb == 2 ? c10 : c11;
+            }
+            // Both planes at once as {Cb, Cr} pairs when every block of the wave passes PK_RES_MAX
+            // in both planes (the scaled DC included; lossless MBs do not use the transform).  A
+            // block's sum is over its four lanes, of the larger of the lane's two plane sums: never
+            // below either plane's own.  (|k| <= 2^27: no wrap.)
+            bool pk = (H264R_INTER_FAST & 1) != 0;
+            if (pk) {
+                uint32_t gs[2];
+    #pragma unroll
+                for (int pl = 0; pl < 2; ++pl)
+                    gs[pl] = abs_acc_biased(k[pl][0][0], abs_acc_biased(k[pl][0][1], abs_acc_biased(k[pl][1][0], abs_acc_biased(k[pl][1][1], 0))));
+                int m = byp ? 0 : (int)max(gs[0], gs[1]);
+                int o = lane_xor1(m);
+                asm volatile("" : "+v"(o));              // a move, not a fold into the add (tests/test_isa.py)
+                m = (int)((uint32_t)m + (uint32_t)o);
+                int lo = lane_lo4(m), hi = lane_hi4(m);
+                asm volatile("" : "+v"(lo), "+v"(hi));
+                pk = !__any((uint32_t)lo + (uint32_t)hi > PK_RES_MAX);
+            }
+            if (pk) {
+                s16x2 K[2][2];
+    #pragma unroll
+                for (int r = 0; r < 2; ++r)
+    #pragma unroll
+                    for (int c = 0; c < 2; ++c) K[r][c] = pk_lo(k[0][r][c], k[1][r][c]);
+                K[0][0] += splat16(dcl_lane ? 32 : 0);   // the rounding, on both planes' DC
                 // rows: my 2 columns + the 2 of lane ^ 1
-                int t[2][2];
+                s16x2 t[2][2];
     #pragma unroll
                 for (int r = 0; r < 2; ++r) {
-                    const int o0 = lane_xor1(k[r][0]), o1 = lane_xor1(k[r][1]);
-                    const int d0 = cc ? o0 : k[r][0], d1 = cc ? o1 : k[r][1], d2 = cc ? k[r][0] : o0, d3 = cc ? k[r][1] : o1;
-                    int y0, y1, y2, y3;
-                    idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                    t[r][0] = cc ? y2 : y0;
-                    t[r][1] = cc ? y3 : y1;
+                    const s16x2 o0 = as_s16x2((uint32_t)lane_xor1((int)as_u32(K[r][0]))), o1 = as_s16x2((uint32_t)lane_xor1((int)as_u32(K[r][1])));
+                    s16x2 d0 = cc ? o0 : K[r][0], d1 = cc ? o1 : K[r][1], d2 = cc ? K[r][0] : o0, d3 = cc ? K[r][1] : o1;
+                    idct4_pk(d0, d1, d2, d3);
+                    t[r][0] = cc ? d2 : d0;
+                    t[r][1] = cc ? d3 : d1;
                 }
                 // columns: my 2 rows + the 2 of lane ^ 4
+                s16x2 rc2[2][2];
     #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    // (rows 0..1 from the lane with by even, 2..3 from the other)
-                    const int d0 = lane_lo4(t[0][c]), d1 = lane_lo4(t[1][c]), d2 = lane_hi4(t[0][c]), d3 = lane_hi4(t[1][c]);
-                    int y0, y1, y2, y3;
-                    idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                    rc[0][c] = ((cr ? y2 : y0) + 32) >> 6;
-                    rc[1][c] = ((cr ? y3 : y1) + 32) >> 6;
+                    const int t0 = (int)as_u32(t[0][c]), t1 = (int)as_u32(t[1][c]);
+                    s16x2 d0 = as_s16x2((uint32_t)lane_lo4(t0)), d1 = as_s16x2((uint32_t)lane_lo4(t1));
+                    s16x2 d2 = as_s16x2((uint32_t)lane_hi4(t0)), d3 = as_s16x2((uint32_t)lane_hi4(t1));
+                    idct4_pk(d0, d1, d2, d3);
+                    rc2[0][c] = (cr ? d2 : d0) >> splat16(6);
+                    rc2[1][c] = (cr ? d3 : d1) >> splat16(6);
                 }
-                // lossless: the raw levels, DC at (0,0) (transform.cc:453-455,860); an inter MB's
-                // intra_chroma_pred_mode is DC (macroblock_t::init slice_data.cc:482), so
-                // bypass_chroma (:802-822) copies
-                if (byp) {
-                    const int dcl = cb == 0 ? c00 : cb == 1 ? c01 : cb == 2 ? c10 : c11;
     #pragma unroll
-                    for (int r = 0; r < 2; ++r)
+                for (int r = 0; r < 2; ++r) {
+                    rcp[0][r] = pk_lo(as_u32(rc2[r][0]), as_u32(rc2[r][1]));
+                    rcp[1][r] = pk_hi(as_u32(rc2[r][0]), as_u32(rc2[r][1]));
+                }
+            } else {
     #pragma unroll
-                        for (int c = 0; c < 2; ++c) rc[r][c] = (cr == 0 && cc == 0 && r == 0 && c == 0) ? dcl : raw[r][c];
+                for (int pl = 0; pl < 2; ++pl) {
+                    // rows: my 2 columns + the 2 of lane ^ 1
+                    int t[2][2], rc[2][2];
+    #pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const int k0 = (int)(k[pl][r][0] - DQ4_BIAS), k1 = (int)(k[pl][r][1] - DQ4_BIAS);
+                        const int o0 = lane_xor1(k0), o1 = lane_xor1(k1);
+                        const int d0 = cc ? o0 : k0, d1 = cc ? o1 : k1, d2 = cc ? k0 : o0, d3 = cc ? k1 : o1;
+                        int y0, y1, y2, y3;
+                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
+                        t[r][0] = cc ? y2 : y0;
+                        t[r][1] = cc ? y3 : y1;
+                    }
+                    // columns: my 2 rows + the 2 of lane ^ 4
+    #pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        // (rows 0..1 from the lane with by even, 2..3 from the other)
+                        const int d0 = lane_lo4(t[0][c]), d1 = lane_lo4(t[1][c]), d2 = lane_hi4(t[0][c]), d3 = lane_hi4(t[1][c]);
+                        int y0, y1, y2, y3;
+                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
+                        rc[0][c] = ((cr ? y2 : y0) + 32) >> 6;
+                        rc[1][c] = ((cr ? y3 : y1) + 32) >> 6;
+                    }
+                    rcp[pl][0] = pk_sat(rc[0][0], rc[0][1]);
+                    rcp[pl][1] = pk_sat(rc[1][0], rc[1][1]);
                 }
             }
+            // lossless: the raw levels, DC at (0,0) (transform.cc:453-455,860); an inter MB's
+            // intra_chroma_pred_mode is DC (macroblock_t::init slice_data.cc:482), so
+            // bypass_chroma (:802-822) copies.  A row's two levels are its loaded word.
+            if (byp) {
+    #pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    rcp[pl][0] = dcl_lane ? pk_hi((uint32_t)dcl[pl] << 16, clev[pl][0]) : as_s16x2(clev[pl][0]);
+                    rcp[pl][1] = as_s16x2(clev[pl][1]);
+                }
+            }
+        }
+    #pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
             uint8_t* cdst = rmb + coff + pl * 64;
     #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const uint32_t pr = predC[pl] >> (16 * r);
-                const uint32_t wv = (uint32_t)clip255((int)(pr & 255) + rc[r][0]) |
-                                    ((uint32_t)clip255((int)((pr >> 8) & 255) + rc[r][1]) << 8);
-                *reinterpret_cast<uint16_t*>(cdst + r * 8) = (uint16_t)wv;
+                const s16x2 pr = as_s16x2(__builtin_amdgcn_perm(0, predC[pl], r ? 0x0c030c02u : 0x0c010c00u));
+                const s16x2 sv = pk_clip255(__builtin_elementwise_add_sat(pr, rcp[pl][r]));
+                *reinterpret_cast<uint16_t*>(cdst + r * 8) = (uint16_t)__builtin_amdgcn_perm(0, as_u32(sv), 0x0c0c0200u);
             }
         }
     }();
