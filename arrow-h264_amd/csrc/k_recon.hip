@@ -7,7 +7,7 @@
 //           RefPicList[l][ref_idx] resolved to a DPB slot through an LDS copy of the
 //           picture's slice tables.
 #include "launch_cfg.h"
-#include "mb_inter4.h"
+#include "mb_inter_sp.h"
 
 using namespace h264r;
 
@@ -65,7 +65,7 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // k_inter4r: per 16-MB group of a workgroup, first the deblocking records DbInfo of the group's
 // MBs (dbinfo_block: their neighbour records and motion are loaded with the group's own record and
 // motion), then the reconstruction of its inter and I_PCM MBs (inter4_mbs); the records' registers
-// are dead before the motion compensation starts (126 VGPRs, 4 waves/SIMD).  Round 6 folded the
+// are dead before the motion compensation starts (125 VGPRs, 4 waves/SIMD).  Round 6 folded the
 // records' own kernel (k_dbinfo, 1.2 ms per 1024 config-3 pictures at 8 waves/SIMD) into it:
 // config 3 11.96 -> 11.78 ms, config 4 4.64 -> 4.53 ms; all-intra config 2 13.87 -> 14.15 ms
 // (its records now run at 4 waves/SIMD; profiles/r06_e_fused_dbinfo_ab.txt).
@@ -110,21 +110,18 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
     for (;;) {
         if (a0 >= aend) return;
         {
-            const int a = a0 + (lane >> 4);
-            const bool valid = a < aend;
-            const int aa = valid ? a : aend - 1;
             const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
             // P pictures: the records without the list-1 motion words and with the one-list comparison
             const bool one = (H264R_INTER_FAST & 2) && inter4_one_list(pre, nb);
             uint2 m1 = inter4_no_list();
             if (!one) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, pre.q.slice, 1);
             if (!(H264R_INTER_DIAG & 32))
-                dbinfo_block(b, g, pic, aa, valid, lane & 15, S, T, pre.q, m0, m1, slice_hdr(slices, S, pre.q.slice), nb,
-                             dbinfo + (size_t)pic * g.nmb, one);
+                dbinfo_block(b, pic, inter4_lane(g, a0, aend, lane), S, T, pre.q, m0, m1,
+                             slice_hdr(slices, S, pre.q.slice), nb, dbinfo + (size_t)pic * g.nmb, one);
         }
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        inter4_mbs<false>(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+        inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
         if (++grp >= gend) return;
         a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;
         int ln2 = lane;
@@ -153,7 +150,7 @@ extern "C" __global__ __launch_bounds__(256) void k_inter_sp(h264r_batch b, int2
         inter4_lds(b, pic, S);
         __syncthreads();
         const int a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;
-        if (a0 < aend) inter4_mbs<true>(b, g, pic, a0, aend, lane, S, nullptr, inter4_pre(b, g, pic, a0, aend, lane), recon, 0);
+        if (a0 < aend) inter4_sp_mbs(b, g, pic, a0, aend, lane, S, recon);
     }
 }
 

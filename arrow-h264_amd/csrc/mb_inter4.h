@@ -24,6 +24,13 @@
 // samples (2bx.., 2by..) of each plane (4:2:0: the chroma of a luma 4x4 block, with
 // the same motion vector).  A chroma 4x4 transform block is spread over the lanes
 // {blk, blk^1, blk^4, blk^5}; an 8x8 luma transform block likewise.
+//
+// inter4_mbs (k_inter4r, at the end of the file) is a sequence of stages, each a function whose
+// parameters are what it reads and writes: inter4_lane (Inter4Lane, the roles above) -> the gate
+// (invalid / intra / SP / inter4_pcm) -> inter4_predict -> inter4_res_load (Inter4Res) ->
+// inter4_luma_residual (luma_res_bypass / luma_res_4x4 / luma_res_8x8) -> inter4_store_luma ->
+// inter4_chroma_residual -> inter4_store_chroma.  The inter MBs of SP slices are k_inter_sp's:
+// inter4_sp_mbs (mb_inter_sp.h), on the same lane roles, prediction and residual inputs.
 #pragma once
 #include "mb_deblock.h"
 
@@ -36,7 +43,8 @@
 #endif
 // H264R_INTER_FAST: the two shortcuts of k_inter4r, each wave-uniform with today's code as the other
 // branch, so either can be A/B'd alone (make EXTRA=-DH264R_INTER_FAST=<bits>): 1 the residual and
-// the construction on packed 16-bit pairs (inter4_mbs<false>), 2 one-list deblocking records
+// the construction on packed 16-bit pairs (the PK parameter of luma_res_4x4 and
+// inter4_chroma_residual), 2 one-list deblocking records (k_recon.hip)
 #ifndef H264R_INTER_FAST
 #define H264R_INTER_FAST 3
 #endif
@@ -52,6 +60,34 @@ struct Inter4Lds {
     int8_t ref_slot[INTER4_LDS_SLICES][2][H264R_MAX_REFS];   // h264r_slice::ref_slot of the picture's slices
     uint8_t slice_type[INTER4_LDS_SLICES];                   // h264r_slice::slice_type of the same slices
 };
+
+// A lane's roles ("Lane roles" above) for the MBs a0 .. a0+3 of a picture.
+struct Inter4Lane {
+    int blk, bx, by;   // my 4x4 block of the MB, raster
+    int aa;            // my MB's address (the range's last MB for the lanes past its end)
+    bool valid;        // my MB is one of the range's
+    int mbx, mby;      // my MB in the picture
+    int X4, Y4;        // my block in the picture, in 4x4 units
+    int b8;            // my 8x8 block: its levels, and its transform in a T8x8 MB
+    int cb, cr, cc;    // my chroma 4x4 block of each plane (= b8) and my 2x2 quadrant of it: rows cr.., cols cc..
+    int yoff, coff;    // my block's first luma row and my Cb quadrant (Cr 64 bytes on) in the MB's 384 bytes of the
+                       // MB-tiled reconstruction (device_common.h recon_mb): rows of 16 / 8 bytes
+};
+DEV Inter4Lane inter4_lane(const Geom& g, int a0, int aend, int lane)
+{
+    Inter4Lane L;
+    const int blk = lane & 15, bx = blk & 3, by = blk >> 2, a = a0 + (lane >> 4);
+    L.blk = blk; L.bx = bx; L.by = by;
+    L.valid = a < aend;
+    L.aa = L.valid ? a : aend - 1;
+    L.mbx = L.aa % g.wmb; L.mby = L.aa / g.wmb;
+    L.X4 = L.mbx * 4 + bx; L.Y4 = L.mby * 4 + by;
+    L.b8 = L.cb = (by >> 1) * 2 + (bx >> 1);
+    L.cr = (by & 1) * 2; L.cc = (bx & 1) * 2;
+    L.yoff = (by * 4) * 16 + bx * 4;
+    L.coff = RECON_CB + (by * 2) * 8 + bx * 2;
+    return L;
+}
 
 // Byte `off` of slice `slice`'s h264r_slice, for the slices past the LDS copy: a buffer
 // load (a select between an LDS and a global byte became one flat load, whose wait covers
@@ -118,13 +154,11 @@ struct Inter4Pre {
 };
 DEV Inter4Pre inter4_pre(const h264r_batch& b, const Geom& g, int pic, int a0, int aend, int lane)
 {
-    const int blk = lane & 15, a = a0 + (lane >> 4);
-    const int aa = a < aend ? a : aend - 1;
-    const int mbx = aa % g.wmb, mby = aa / g.wmb;
-    const int mi = (mby * 4 + (blk >> 2)) * g.W4 + mbx * 4 + (blk & 3);
+    const Inter4Lane L = inter4_lane(g, a0, aend, lane);
+    const int mi = L.Y4 * g.W4 + L.X4;
     const size_t mbase = (size_t)pic * 2 * g.motion_plane;
     Inter4Pre p;
-    p.q = mb_lane(&b.mbs[(size_t)pic * g.nmb + aa]);
+    p.q = mb_lane(&b.mbs[(size_t)pic * g.nmb + L.aa]);
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
         p.mv[l] = b.mv[mbase + l * g.motion_plane + mi];
@@ -144,17 +178,14 @@ struct DbNb {
 };
 DEV DbNb dbinfo_pre(const h264r_batch& b, const Geom& g, int pic, int a0, int aend, int lane)
 {
-    const int blk = lane & 15, a = a0 + (lane >> 4);
-    const int aa = a < aend ? a : aend - 1;
-    const int mbx = aa % g.wmb, mby = aa / g.wmb;
-    const int X4 = mbx * 4 + (blk & 3), Y4 = mby * 4 + (blk >> 2);
-    const int mi = Y4 * g.W4 + X4;
-    const int li = X4 > 0 ? mi - 1 : mi, ui = Y4 > 0 ? mi - g.W4 : mi;
+    const Inter4Lane L = inter4_lane(g, a0, aend, lane);
+    const int aa = L.aa, mi = L.Y4 * g.W4 + L.X4;
+    const int li = L.X4 > 0 ? mi - 1 : mi, ui = L.Y4 > 0 ? mi - g.W4 : mi;
     const size_t mbase = (size_t)pic * 2 * g.motion_plane;
     const h264r_mb* mbs = b.mbs + (size_t)pic * g.nmb;
     DbNb n;
-    n.L = mb_lane(&mbs[mbx > 0 ? aa - 1 : aa]);
-    n.U = mb_lane(&mbs[mby > 0 ? aa - g.wmb : aa]);
+    n.L = mb_lane(&mbs[L.mbx > 0 ? aa - 1 : aa]);
+    n.U = mb_lane(&mbs[L.mby > 0 ? aa - g.wmb : aa]);
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
         n.lmv[l] = b.mv[mbase + l * g.motion_plane + li];
@@ -473,48 +504,13 @@ DEV void idct4_inplace(int& a, int& b, int& c, int& d)
     idct4(a, b, c, d, o0, o1, o2, o3);
     a = o0; b = o1; c = o2; d = o3;
 }
-
-// ------------------------------------------------------------------ SP slices
-// Transform::itrans_sp / itrans_sp_cr (transform.cc:1098-1265), the arithmetic of the
-// reference as it stands (see oracle/h264r_oracle.c sp_mb for its quirks).
-__device__ static const uint8_t SP_A[16] = {16, 20, 16, 20, 20, 25, 20, 25, 16, 20, 16, 20, 20, 25, 20, 25};
-DEV int sp_sgn(int x) { return (x >= 0) - (x < 0); }                                   // defines.h:73-77
-DEV int sp_ls2(int m, int j, int i)                                                     // LevelScale2 :1105-1130
+// rows then columns of a 4x4 block in registers
+DEV void idct4x4_inplace(int (&d)[4][4])
 {
-    const int cls = (j & 1) + (i & 1);
-    constexpr int v0[6] = {13107, 11916, 10082, 9362, 8192, 7282};
-    constexpr int v1[6] = {8066, 7490, 6554, 5825, 5243, 4559};
-    constexpr int v2[6] = {5243, 4660, 4194, 3647, 3355, 2893};
-    return cls == 0 ? v0[m] : (cls == 1 ? v1[m] : v2[m]);
-}
-DEV int sp_dq(int m, int j, int i)                                                      // dequant_coef :93-100
-{
-    constexpr int v0[6] = {10, 11, 13, 14, 16, 18};
-    constexpr int v1[6] = {13, 14, 16, 18, 20, 23};
-    constexpr int v2[6] = {16, 18, 20, 23, 25, 29};
-    const int cls = (j & 1) + (i & 1);
-    return cls == 0 ? v0[m] : (cls == 1 ? v1[m] : v2[m]);
-}
-// One coefficient of itrans_sp (luma, :1158-1178): cr the dequantised level, cp the
-// transformed prediction; returns the re-dequantised coefficient.
-DEV int sp_luma_coef(int cr, int cp, int j, int i, int qp, int qs, int sw)
-{
-    const int ls = sp_ls2(qs % 6, j, i);
-    int cij;
-    if (sw) {
-        cij = cr + sp_sgn(cp) * ((iabs(cp) * ls + (1 << (14 + qs / 6))) >> (15 + qs / 6));
-    } else {
-        const int cs = cp + ((int)((unsigned)(cr * sp_dq(qp % 6, j, i) * SP_A[j * 4 + i]) << (qp / 6)) >> 10);
-        cij = sp_sgn(cs) * ((iabs(cs) * ls + (1 << (14 + qs / 6))) >> (15 + qs / 6));
-    }
-    const int dq = sp_dq(qs % 6, j, i);
-    return qs >= 24 ? (int)((unsigned)(cij * dq) << (qs / 6 - 4)) : (cij * dq + (1 << (3 - qs / 6))) >> (4 - qs / 6);
-}
-// 4-point forward core transform (forward_4x4 rows / columns, :560-594)
-DEV void fwd4(int p0, int p1, int p2, int p3, int& c0, int& c1, int& c2, int& c3)
-{
-    const int e0 = p0 + p3, e1 = p1 + p2, e2 = p1 - p2, e3 = p0 - p3;
-    c0 = e0 + e1; c1 = e2 + (e3 << 1); c2 = e0 - e1; c3 = e3 - (e2 << 1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) idct4_inplace(d[i][0], d[i][1], d[i][2], d[i][3]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) idct4_inplace(d[0][c], d[1][c], d[2][c], d[3][c]);
 }
 
 // QpY (pl 0) / QpC[pl - 1] of a record, from its dwords 0 and 1
@@ -604,13 +600,12 @@ DEV void dbinfo_records(const h264r_mb& q, const h264r_mb& L, const h264r_mb& U,
 // k_inter4r, before the group's reconstruction.
 // `one` (wave-uniform, inter4_one_list): no list-1 motion in reach of any lane; m1 is then
 // inter4_no_list().
-DEV void dbinfo_block(const h264r_batch& b, const Geom& g, int pic, int aa, bool valid, int blk, const Inter4Lds& S, const DbTables& T,
+DEV void dbinfo_block(const h264r_batch& b, int pic, const Inter4Lane& ln, const Inter4Lds& S, const DbTables& T,
                       const h264r_mb& q, uint2 m0, uint2 m1, uint2 qsh, const DbNb& nb, DbInfo* __restrict__ dbout, bool one)
 {
-    const int bx = blk & 3, by = blk >> 2;
-    const int mbx = aa % g.wmb, mby = aa / g.wmb;
+    const int bx = ln.bx, by = ln.by;
     const h264r_slice* slices = b.slices + (size_t)pic * b.slice_stride;
-    const int hasL = mbx > 0, hasU = mby > 0;
+    const int hasL = ln.mbx > 0, hasU = ln.mby > 0;
     const h264r_mb& L = nb.L;
     const h264r_mb& U = nb.U;
     // the neighbour block belongs to this MB or to the left / upper one (its slice resolves it)
@@ -628,692 +623,575 @@ DEV void dbinfo_block(const h264r_batch& b, const Geom& g, int pic, int aa, bool
     // ---- deblocking record (Deblock::strength deblock.cc:78-289): this lane's
     // left edge (vertical edge bx, segment by) and top edge (horizontal edge by,
     // segment bx)
-    if (valid) {
+    if (ln.valid) {
         const MotionRef mq = motion_of(m0, m1), ml = motion_of(l0, l1), mu = motion_of(u0, u1);
         // bs_compare_one also needs a list-0 reference on one side of every edge it is asked about.
         // Only edges between two inter MBs reach the comparison, so an inter MB's block without one
         // (no conforming stream has it: ref_idx out of range, or an empty RefPicList entry) sends
         // the wave to bs_compare.
         if (one) one = !__any(!mb_is_intra(q) && mq.ref[0] < 0 && (ml.ref[0] < 0 || mu.ref[0] < 0));
-        DbInfo* out = dbout + aa;
-        if (one) dbinfo_records<true>(q, L, U, mq, ml, mu, blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
-        else dbinfo_records<false>(q, L, U, mq, ml, mu, blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+        DbInfo* out = dbout + ln.aa;
+        if (one) dbinfo_records<true>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+        else dbinfo_records<false>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
     }
 }
 
-// The inter / I_PCM macroblocks a0 .. a0+3 of picture `pic` (their deblocking records come
-// first, dbinfo_block).  SP = false (k_inter4r): inter MBs of SP slices are left out and flagged in
-// *sp_flag (the launch tag); SP = true (k_inter_sp): only those are reconstructed, with inverse_transform_sp
-// (decoder.cc:256-257, transform.cc:1267-1300).
-template <bool SP>
+// ------------------------------------------------------------------ the stages of inter4_mbs
+// I_PCM: the samples as the level buffer holds them (mb_pred_ipcm decoder.cc:149-168)
+DEV void inter4_pcm(uint8_t* rmb, const Inter4Lane& L, const int16_t* lv)
+{
+    const uint8_t* raw = reinterpret_cast<const uint8_t*>(lv);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        *reinterpret_cast<uint32_t*>(rmb + L.yoff + r * 16) = *reinterpret_cast<const uint32_t*>(raw + (L.by * 4 + r) * 16 + L.bx * 4);
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            *reinterpret_cast<uint16_t*>(rmb + L.coff + pl * 64 + r * 8) =
+                *reinterpret_cast<const uint16_t*>(raw + 256 + pl * 64 + (L.by * 2 + r) * 8 + L.bx * 2);
+}
+
+// The prediction of my block: the motion compensation of each list it uses (m0 / m1: motion_word),
+// combined by the slice's weighted prediction (qs, wp_mode).  predY[i]: luma row i's four samples as
+// bytes; predC[pl]: my 2x2 chroma samples of plane pl (chroma_block_pred2).
+DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inter4Lane& L, const Inter4Lds& S,
+                        const h264r_slice* __restrict__ qs, int wp_mode, uint2 m0, uint2 m1, uint32_t (&predY)[4],
+                        uint32_t (&predC)[2])
+{
+    const int r0 = (int8_t)(m0.y & 255), r1 = (int8_t)(m1.y & 255);
+    const int dir = (r0 >= 0 && r1 >= 0) ? 2 : (r0 >= 0 ? 0 : 1);
+    // the prediction of each list in named registers: an array indexed by the (not
+    // unrolled) list loop was promoted to LDS by the compiler (48 B per lane)
+    uint32_t pY[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, pC[2][2] = {{0, 0}, {0, 0}};
+    // a field picture (include/h264r.h H264R_TOP_FIELD) reads fields of the DPB frames:
+    // every second row from the field's first row, clamped to the field's own rows
+    const int structure = (int)__builtin_amdgcn_readfirstlane(ld_const(&b.pics[pic].structure));
+    // an MBAFF picture of a mixed batch counts as a field picture here and in dbinfo_block
+    const int fld = structure != H264R_FRAME;
+#pragma unroll 1
+    for (int l = 0; l < 2; ++l) {
+        const uint2 mw = l ? m1 : m0;
+        const int rr = l ? r1 : r0;
+        const bool use = rr >= 0;
+        if (!__any(use)) continue;                                  // P pictures: list 1 never
+        uint32_t tY[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
+        uint32_t tC[2] = {0x80808080u, 0x80808080u};                // no_ref: 128 (inter_prediction.cc:164-167,366-369)
+        const int ref = (int8_t)((mw.y >> 8) & 255);                // slot | H264R_REF_BOTTOM
+        const int slot = ref & 31, bot = fld & (ref >> 6);
+        const bool ok = use && ref >= 0 && (ref & ~H264R_REF_BOTTOM) < H264R_MAX_SLOTS && rr < H264R_MAX_REFS &&
+                        S.planes[slot * 3];
+        const int mvx = (int16_t)(mw.x & 0xFFFF), mvy = (int16_t)(mw.x >> 16);
+        const int vx = L.X4 * 16 + mvx, vy = L.Y4 * 16 + mvy;       // quarter luma / eighth chroma units
+        const int x = vx >> 2, y = vy >> 2;
+        {
+            // the 9 window rows of the lane's own block, straight from the plane
+            uint32_t w[9][3];
+            if constexpr (H264R_INTER_DIAG & 4) {
+                // diagnostic build (wrong output): no window loads, no luma filter
+                tY[0] = tY[1] = tY[2] = tY[3] = (uint32_t)(vx ^ vy);
+            } else {
+                if (ok) luma_window_global(S.planes[slot * 3] + bot * g.W, g.W, g.W << fld, g.H, x, y, w);
+                if constexpr (H264R_INTER_DIAG & 2) {
+                    // diagnostic build (wrong output): the window loads without the luma filter
+                    if (ok) {
+                        uint32_t acc = 0;
+#pragma unroll
+                        for (int r = 0; r < 9; ++r) acc ^= w[r][0] ^ w[r][1] ^ w[r][2];
+                        tY[0] = tY[1] = tY[2] = tY[3] = acc;
+                    }
+                } else {
+                    if (ok) luma_block_pred(w, g.W, x, vx & 3, vy & 3, tY);
+                }
+            }
+        }
+        // a reference field of the other parity: the chroma sample grid sits a quarter
+        // chroma row off (get_block_chroma inter_prediction.cc:352-355)
+        const int vyc = vy + (fld && bot != (structure == H264R_BOTTOM_FIELD) ? (bot ? -2 : 2) : 0);
+        if constexpr (H264R_INTER_DIAG & 8) {
+            tC[0] = tC[1] = (uint32_t)vyc;        // diagnostic build (wrong output): no chroma MC
+        } else {
+            if (ok) chroma_block_pred2(S.planes[slot * 3 + 1] + bot * g.Wc, S.planes[slot * 3 + 2] + bot * g.Wc, g.Wc,
+                                       g.Wc << fld, g.Hc, vx >> 3, vyc >> 3, vx & 7, vyc & 7, tC);
+        }
+        const bool l1 = l != 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            pY[0][i] = (use && !l1) ? tY[i] : pY[0][i];
+            pY[1][i] = (use && l1) ? tY[i] : pY[1][i];
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            pC[0][k] = (use && !l1) ? tC[k] : pC[0][k];
+            pC[1][k] = (use && l1) ? tC[k] : pC[1][k];
+        }
+    }
+    WpPar wpp[3] = {};
+    if (wp_mode != 0) {
+        const WpRaw wr = wp_raw(qs, r0, r1);
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) wpp[pl] = wp_params(wr, wp_mode, dir, pl);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) predY[i] = wp_combine4(wpp[0], wp_mode, dir, pY[0][i], pY[1][i]);
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) predC[pl] = wp_combine4(wpp[1 + pl], wp_mode, dir, pC[0][pl], pC[1][pl]);
+}
+
+// The residual inputs of my block.  Luma: the 16 levels and scales of my 4x4 block, or of my 4x4
+// quadrant of a T8x8 MB's 8x8 block, raster, four 16-bit values per dword pair.  Chroma, per plane: rows
+// cr, cr + 1 of my quadrant (two 16-bit values per dword), the plane's four DC levels and the DC scale.
+// Zero where the MB codes nothing.
+struct Inter4Res {
+    uint4 lev[2], lsc[2];
+    uint32_t clev[2][2], csc[2][2];
+    uint2 cdc[2];
+    int cdcs[2];
+};
+DEV Inter4Res inter4_res_load(const h264r_mb& q, const Inter4Lane& L, const int16_t* lv, const h264r_quant* __restrict__ qt)
+{
+    Inter4Res R = {};
+    const int cbpc = q.cbp >> 4, qpl = q.qp_scaled[0];
+    const int by = L.by, bx = L.bx;
+    const int loff = b8_offset(q.cbp, L.b8);
+    if (loff >= 0) {
+        if (!(q.flags & H264R_MBF_T8x8)) {      // 4x4 block: 16 raster levels
+            const uint4* p = reinterpret_cast<const uint4*>(lv + loff + ((by & 1) * 2 + (bx & 1)) * 16);
+            R.lev[0] = p[0]; R.lev[1] = p[1];
+            const uint4* s = reinterpret_cast<const uint4*>(&qt->scale4x4[1][0][qpl % 6][0]);
+            R.lsc[0] = s[0]; R.lsc[1] = s[1];
+        } else {                                // my 4x4 quadrant of the 8x8 block: rows (by&1)*4.., cols (bx&1)*4..
+            const int16_t* p = lv + loff + (by & 1) * 32 + (bx & 1) * 4;
+            const int16_t* s = &qt->scale8x8[1][0][qpl % 6][(by & 1) * 32 + (bx & 1) * 4];
+            const uint2 r0 = ld8(p), r1 = ld8(p + 8), r2 = ld8(p + 16), r3 = ld8(p + 24);
+            R.lev[0] = make_uint4(r0.x, r0.y, r1.x, r1.y); R.lev[1] = make_uint4(r2.x, r2.y, r3.x, r3.y);
+            const uint2 s0 = ld8(s), s1 = ld8(s + 8), s2 = ld8(s + 16), s3 = ld8(s + 24);
+            R.lsc[0] = make_uint4(s0.x, s0.y, s1.x, s1.y); R.lsc[1] = make_uint4(s2.x, s2.y, s3.x, s3.y);
+        }
+    }
+    if (cbpc) {
+        const LevelOffs lo = level_offsets(q);
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            const int qpc = q.qp_scaled[1 + pl];
+            R.cdc[pl] = ld8(lv + lo.cdc + pl * 4);
+            R.cdcs[pl] = qt->scale4x4[1][1 + pl][qpc % 6][0];
+            if (cbpc == 2) {
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    R.clev[pl][r] = *reinterpret_cast<const uint32_t*>(lv + lo.cac + pl * 64 + L.cb * 16 + (L.cr + r) * 4 + L.cc);
+                    R.csc[pl][r] = *reinterpret_cast<const uint32_t*>(&qt->scale4x4[1][1 + pl][qpc % 6][(L.cr + r) * 4 + L.cc]);
+                }
+            }
+        }
+    }
+    return R;
+}
+// Luma level / scale (i, c) of my block
+DEV int res_at(const uint4 (&w)[2], int i, int c) { return sel16((i & 1) ? w[i >> 1].z : w[i >> 1].x, (i & 1) ? w[i >> 1].w : w[i >> 1].y, c); }
+DEV int level_at(const Inter4Res& R, int i, int c) { return res_at(R.lev, i, c); }
+DEV int scale_at(const Inter4Res& R, int i, int c) { return res_at(R.lsc, i, c); }
+// dq4 / dq8 (transform.cc:394-419) as one form, rounding and shift per lane: the lanes of a wave
+// mix 4x4 and 8x8 MBs, and a select per value (not a branch) keeps the 16 values free of
+// exec-mask work
+DEV void luma_dequant(const Inter4Res& R, int per, int t8, int (&d)[4][4])
+{
+    const int drnd = t8 ? 32 : 8, dsh = t8 ? 6 : 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[i][c] = ((level_at(R, i, c) * scale_at(R, i, c)) * (1 << per) + drnd) >> dsh;
+}
+// the 32-bit paths' result, saturated (pk_sat)
+DEV void pack_res(const int (&res)[4][4], s16x2 (&rp)[4][2])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        rp[i][0] = pk_sat(res[i][0], res[i][1]);
+        rp[i][1] = pk_sat(res[i][2], res[i][3]);
+    }
+}
+
+// Lossless MBs (TransformBypassModeFlag): the levels are the residual, DPCM'd in place down
+// the columns / along the rows when the block's Intra4x4PredMode / Intra8x8PredMode is vertical /
+// horizontal (bypass_4x4 / bypass_8x8 transform.cc:736-778; inverse_transform_4x4 / _8x8 :986-1016
+// read those modes for inter MBs too: whatever the parser's mb_t slot holds).  The flag is
+// uniform over an MB's 16 lanes, so the cross-lane carries stay inside the caller's branch.
+DEV void luma_res_bypass(const h264r_mb& q, const Inter4Lane& L, const Inter4Res& R, int t8, s16x2 (&rp)[4][2])
+{
+    const int bx = L.bx, by = L.by;
+    int d[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[i][c] = level_at(R, i, c);
+    const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
+    const uint64_t ipw = (uint64_t)qw[5] | ((uint64_t)qw[6] << 32);
+    const int bk = t8 ? L.b8 : (by >> 1) * 8 + (bx >> 1) * 4 + (by & 1) * 2 + (bx & 1);
+    const int mode = (int)((ipw >> (4 * bk)) & 15);
+    const bool vert = mode == 0, horz = mode == 1;
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[i][c] += vert ? d[i - 1][c] : 0;
+#pragma unroll
+    for (int c = 1; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i][c] += horz ? d[i][c - 1] : 0;
+    // 8x8: the quadrant above (lane ^ 4) / to the left (lane ^ 1) carries in
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int up = lane_xor4(d[3][c]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i][c] += (t8 && vert && (by & 1)) ? up : 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int left = lane_xor1(d[i][3]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) d[i][c] += (t8 && horz && (bx & 1)) ? left : 0;
+    }
+    pack_res(d, rp);
+}
+
+// 4x4 blocks in every lane of the wave: all in-lane.  PK: on 16-bit pairs when every lane's block
+// passes PK_RES_MAX (real content does): rows 0, 1 and rows 2, 3 as the halves of two transforms, a
+// 2x2 transpose of the pairs, then columns {0, 1} and {2, 3}
+template <bool PK>
+DEV void luma_res_4x4(const Inter4Res& R, int per, int t8, s16x2 (&rp)[4][2])
+{
+    bool pk = PK;
+    uint32_t u[4][4];
+    if (pk) {
+        uint32_t gs = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                u[i][c] = dq4_biased(level_at(R, i, c), scale_at(R, i, c), per);
+                gs = abs_acc_biased(u[i][c], gs);
+            }
+        pk = !__any(gs > PK_RES_MAX);
+    }
+    if (pk) {
+        s16x2 A[4], B[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            A[c] = pk_lo(u[0][c], u[1][c]);
+            B[c] = pk_lo(u[2][c], u[3][c]);
+        }
+        A[0] += (s16x2){32, 0};
+        idct4_pk(A[0], A[1], A[2], A[3]);
+        idct4_pk(B[0], B[1], B[2], B[3]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            s16x2 x0 = pk_lo(as_u32(A[2 * h]), as_u32(A[2 * h + 1])), x1 = pk_hi(as_u32(A[2 * h]), as_u32(A[2 * h + 1]));
+            s16x2 x2 = pk_lo(as_u32(B[2 * h]), as_u32(B[2 * h + 1])), x3 = pk_hi(as_u32(B[2 * h]), as_u32(B[2 * h + 1]));
+            idct4_pk(x0, x1, x2, x3);
+            rp[0][h] = x0 >> splat16(6); rp[1][h] = x1 >> splat16(6);
+            rp[2][h] = x2 >> splat16(6); rp[3][h] = x3 >> splat16(6);
+        }
+    } else {
+        // rows then columns, 32-bit (the biased values are the dequantised ones + 2^27,
+        // exactly: taken back, not computed again, so that the range test keeps its
+        // own shift-and-add)
+        int d[4][4], res[4][4];
+        if constexpr (PK) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) d[i][c] = (int)(u[i][c] - DQ4_BIAS);
+        } else {
+            luma_dequant(R, per, t8, d);
+        }
+        idct4x4_inplace(d);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) res[i][c] = (d[i][c] + 32) >> 6;
+        pack_res(res, rp);
+    }
+}
+
+// A wave with T8x8 MBs: their 8x8 transform across the four lanes of an 8x8 block; the 4x4 MBs of
+// the same wave transform in-lane, 32-bit.  Rows: my 4 + the 4 of lane ^ 1.
+DEV void luma_res_8x8(const Inter4Lane& L, const Inter4Res& R, int per, int t8, s16x2 (&rp)[4][2])
+{
+    const int bx = L.bx, by = L.by;
+    int d[4][4], e4[4][4], res[4][4];
+    luma_dequant(R, per, t8, d);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int in[8], outv[8];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int ov = lane_xor1(d[i][c]);
+            in[c] = (bx & 1) ? ov : d[i][c];
+            in[4 + c] = (bx & 1) ? d[i][c] : ov;
+        }
+        idct8(in, outv);
+        // mask select: a ternary over the two halves became a lane-indexed array
+        // read, which the compiler placed in LDS (32 B per lane)
+        const int mx = -(bx & 1);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e4[i][c] = (outv[c] & ~mx) | (outv[4 + c] & mx);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        int in[8], outv[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            in[i] = lane_lo4(e4[i][c]);         // rows 0..3: the lane with by even
+            in[4 + i] = lane_hi4(e4[i][c]);
+        }
+        idct8(in, outv);
+        const int my = -(by & 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) res[i][c] = t8 ? ((outv[i] & ~my) | (outv[4 + i] & my)) : 0;
+    }
+    if (!t8) idct4x4_inplace(d);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) res[i][c] = ((t8 ? res[i][c] : d[i][c]) + 32) >> 6;
+    pack_res(res, rp);
+}
+
+// Luma residual of my block (transform.cc:1058-1073): rp[i][h] = {row i's columns 2h, 2h + 1} as a
+// 16-bit pair, what the construction takes (construct4).  (Each path dequantises for itself: the
+// lossless one takes the levels, the 4x4 one a biased form its range test reads.)
+template <bool PK>
+DEV void inter4_luma_residual(const h264r_mb& q, const Inter4Lane& L, const Inter4Res& R, s16x2 (&rp)[4][2])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rp[i][0] = rp[i][1] = splat16(0);
+    if (!__any((q.cbp & 15) != 0)) return;
+    const int t8 = (q.flags & H264R_MBF_T8x8) != 0, per = q.qp_scaled[0] / 6;
+    if (q.flags & H264R_MBF_BYPASS) luma_res_bypass(q, L, R, t8, rp);
+    else if (!__any(t8 != 0)) luma_res_4x4<PK>(R, per, t8, rp);
+    else luma_res_8x8(L, R, per, t8, rp);
+}
+// H264R_INTER_DIAG 64 (wrong output): the luma levels loaded, not transformed (16: R is empty)
+DEV void luma_res_stub(const Inter4Res& R, s16x2 (&rp)[4][2])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rp[i][0] = rp[i][1] = splat16(0);
+    rp[0][0].x = (short)((R.lev[0].x ^ R.lev[0].y ^ R.lev[0].z ^ R.lev[0].w ^ R.lev[1].x ^ R.lev[1].y ^ R.lev[1].z ^ R.lev[1].w ^
+                          R.lsc[0].x ^ R.lsc[1].y) & 3);
+}
+
+// Construction + store of my 4x4 luma block
+DEV void inter4_store_luma(uint8_t* rmb, const Inter4Lane& L, const uint32_t (&predY)[4], const s16x2 (&rp)[4][2])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<uint32_t*>(rmb + L.yoff + i * 16) = construct4(predY[i], rp[i][0], rp[i][1]);
+}
+// H264R_INTER_DIAG 1 (wrong output): one 16-byte store per lane, an MB's 16 lanes contiguous
+DEV void inter4_store_luma_16b(uint8_t* rmb, const Inter4Lane& L, const uint32_t (&predY)[4], const s16x2 (&rp)[4][2])
+{
+    uint32_t wv4[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wv4[i] = construct4(predY[i], rp[i][0], rp[i][1]);
+    *reinterpret_cast<uint4*>(rmb + L.blk * 16) = make_uint4(wv4[0], wv4[1], wv4[2], wv4[3]);
+}
+
+// A 4x4 block spread over the lanes {blk, ^1, ^4, ^5}, a 2x2 quadrant each (rows cr.., cols cc..):
+// one 1-D pass Op (in place on four values: idct4_inplace, idct4_pk, fwd4_inplace) over the block's
+// rows / columns.  a, b: my two values of the row / column, in and out.
+DEV s16x2 lane_xor1(s16x2 v) { return as_s16x2((uint32_t)lane_xor1((int)as_u32(v))); }
+DEV s16x2 lane_lo4(s16x2 v) { return as_s16x2((uint32_t)lane_lo4((int)as_u32(v))); }
+DEV s16x2 lane_hi4(s16x2 v) { return as_s16x2((uint32_t)lane_hi4((int)as_u32(v))); }
+// rows: my 2 columns + the 2 of lane ^ 1
+template <auto Op, typename T>
+DEV void quad_rows(T& a, T& b, int cc)
+{
+    const T o0 = lane_xor1(a), o1 = lane_xor1(b);
+    T d0 = cc ? o0 : a, d1 = cc ? o1 : b, d2 = cc ? a : o0, d3 = cc ? b : o1;
+    Op(d0, d1, d2, d3);
+    a = cc ? d2 : d0;
+    b = cc ? d3 : d1;
+}
+// columns: my 2 rows + the 2 of lane ^ 4 (rows 0..1 from the lane with by even, 2..3 from the other).
+// XOR4: by lane_xor4 and a select (k_inter_sp's form) instead of lane_lo4 / lane_hi4 -- each kernel
+// keeps the DPP forms the parity suite verified in it (tests/test_isa.py)
+template <auto Op, bool XOR4 = false, typename T>
+DEV void quad_cols(T& a, T& b, int cr)
+{
+    T d0, d1, d2, d3;
+    if constexpr (XOR4) {
+        const T o0 = lane_xor4(a), o1 = lane_xor4(b);
+        d0 = cr ? o0 : a; d1 = cr ? o1 : b; d2 = cr ? a : o0; d3 = cr ? b : o1;
+    } else {
+        d0 = lane_lo4(a); d1 = lane_lo4(b); d2 = lane_hi4(a); d3 = lane_hi4(b);
+    }
+    Op(d0, d1, d2, d3);
+    a = cr ? d2 : d0;
+    b = cr ? d3 : d1;
+}
+
+// Chroma residual of my quadrant (transform.cc:1081-1091, DC :875-889): chroma block cb is spread
+// over lanes {blk, ^1, ^4, ^5}; my quadrant rows cr.., cols cc..
+// rcp[pl][r] = {row r's two samples of plane pl} as a 16-bit pair
+template <bool PK>
+DEV void inter4_chroma_residual(const h264r_mb& q, const Inter4Lane& L, const Inter4Res& R, s16x2 (&rcp)[2][2])
+{
+    const int cb = L.cb, cr = L.cr, cc = L.cc;
+    const int cbpc = q.cbp >> 4;
+    const bool byp = (q.flags & H264R_MBF_BYPASS) != 0;
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) rcp[pl][0] = rcp[pl][1] = splat16(0);
+    if (!__any(cbpc != 0)) return;
+    const bool dcl_lane = cr == 0 && cc == 0;
+    // k: the dequantised coefficients + DQ4_BIAS (dq4_biased), the scaled DC among them
+    uint32_t k[2][2][2];
+    int dcl[2];
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        const int qpc = q.qp_scaled[1 + pl], per = qpc / 6;
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                k[pl][r][c] = dq4_biased((int16_t)(R.clev[pl][r] >> (16 * c)), (int16_t)(R.csc[pl][r] >> (16 * c)), per);
+        const int c00 = (int16_t)(R.cdc[pl].x & 0xFFFF), c01 = (int16_t)(R.cdc[pl].x >> 16);
+        const int c10 = (int16_t)(R.cdc[pl].y & 0xFFFF), c11 = (int16_t)(R.cdc[pl].y >> 16);
+        const int e00 = c00 + c01, e01 = c00 - c01, e10 = c10 + c11, e11 = c10 - c11;
+        // f = (e00 or e01) +/- (e10 or e11) by cb's bits: arithmetic, not a branch tree
+        const int ea = (cb & 1) ? e01 : e00, eb = (cb & 1) ? e11 : e10;
+        const int f = ea + (eb ^ -(cb >> 1)) + (cb >> 1);
+        if (dcl_lane) k[pl][0][0] = (uint32_t)(cbpc ? ((f * R.cdcs[pl]) * (1 << per)) >> 5 : 0) + DQ4_BIAS;
+        dcl[pl] = cb == 0 ? c00 : cb == 1 ? c01 : cb == 2 ? c10 : c11;
+    }
+    // Both planes at once as {Cb, Cr} pairs when every block of the wave passes PK_RES_MAX
+    // in both planes (the scaled DC included; lossless MBs do not use the transform).  A
+    // block's sum is over its four lanes, of the larger of the lane's two plane sums: never
+    // below either plane's own.  (|k| <= 2^27: no wrap.)
+    bool pk = PK;
+    if (pk) {
+        uint32_t gs[2];
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl)
+            gs[pl] = abs_acc_biased(k[pl][0][0], abs_acc_biased(k[pl][0][1], abs_acc_biased(k[pl][1][0], abs_acc_biased(k[pl][1][1], 0))));
+        int m = byp ? 0 : (int)max(gs[0], gs[1]);
+        int o = lane_xor1(m);
+        asm volatile("" : "+v"(o));              // a move, not a fold into the add (tests/test_isa.py)
+        m = (int)((uint32_t)m + (uint32_t)o);
+        int lo = lane_lo4(m), hi = lane_hi4(m);
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        pk = !__any((uint32_t)lo + (uint32_t)hi > PK_RES_MAX);
+    }
+    if (pk) {
+        s16x2 K[2][2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) K[r][c] = pk_lo(k[0][r][c], k[1][r][c]);
+        K[0][0] += splat16(dcl_lane ? 32 : 0);   // the rounding, on both planes' DC
+#pragma unroll
+        for (int r = 0; r < 2; ++r) quad_rows<idct4_pk>(K[r][0], K[r][1], cc);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) quad_cols<idct4_pk>(K[0][c], K[1][c], cr);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const uint32_t r0 = as_u32(K[r][0] >> splat16(6)), r1 = as_u32(K[r][1] >> splat16(6));
+            rcp[0][r] = pk_lo(r0, r1);
+            rcp[1][r] = pk_hi(r0, r1);
+        }
+    } else {
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            int t[2][2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                t[r][0] = (int)(k[pl][r][0] - DQ4_BIAS);
+                t[r][1] = (int)(k[pl][r][1] - DQ4_BIAS);
+                quad_rows<idct4_inplace>(t[r][0], t[r][1], cc);
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) quad_cols<idct4_inplace>(t[0][c], t[1][c], cr);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) rcp[pl][r] = pk_sat((t[r][0] + 32) >> 6, (t[r][1] + 32) >> 6);
+        }
+    }
+    // lossless: the raw levels, DC at (0,0) (transform.cc:453-455,860); an inter MB's
+    // intra_chroma_pred_mode is DC (macroblock_t::init slice_data.cc:482), so
+    // bypass_chroma (:802-822) copies.  A row's two levels are its loaded word.
+    if (byp) {
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+            rcp[pl][0] = dcl_lane ? pk_hi((uint32_t)dcl[pl] << 16, R.clev[pl][0]) : as_s16x2(R.clev[pl][0]);
+            rcp[pl][1] = as_s16x2(R.clev[pl][1]);
+        }
+    }
+}
+// H264R_INTER_DIAG 128 (wrong output): the chroma levels loaded, not transformed (16: R is empty)
+DEV void chroma_res_stub(const Inter4Res& R, s16x2 (&rcp)[2][2])
+{
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        rcp[pl][0] = rcp[pl][1] = splat16(0);
+        rcp[pl][0].x = (short)((R.clev[pl][0] ^ R.clev[pl][1] ^ R.csc[pl][0] ^ R.csc[pl][1] ^ R.cdc[pl].x ^ R.cdc[pl].y ^ (uint32_t)R.cdcs[pl]) & 3);
+    }
+}
+
+// Construction + store of my 2x2 chroma samples of both planes
+DEV void inter4_store_chroma(uint8_t* rmb, const Inter4Lane& L, const uint32_t (&predC)[2], const s16x2 (&rcp)[2][2])
+{
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl) {
+        uint8_t* cdst = rmb + L.coff + pl * 64;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const s16x2 pr = as_s16x2(__builtin_amdgcn_perm(0, predC[pl], r ? 0x0c030c02u : 0x0c010c00u));
+            const s16x2 sv = pk_clip255(__builtin_elementwise_add_sat(pr, rcp[pl][r]));
+            *reinterpret_cast<uint16_t*>(cdst + r * 8) = (uint16_t)__builtin_amdgcn_perm(0, as_u32(sv), 0x0c0c0200u);
+        }
+    }
+}
+
+// The inter / I_PCM macroblocks a0 .. a0+3 of picture `pic` (k_inter4r; their deblocking records come
+// first, dbinfo_block).  Inter MBs of SP slices are left out and flagged in *sp_flag (the launch
+// tag): k_inter_sp's (mb_inter_sp.h).
 DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int aend, int lane,
                     const Inter4Lds& S, int* sp_flag, const Inter4Pre& pre, uint8_t* __restrict__ recon, int tag)
 {
-    const int grp = lane >> 4, blk = lane & 15, bx = blk & 3, by = blk >> 2;
-    const int a = a0 + grp;
-    const bool valid = a < aend;
-    const int aa = valid ? a : aend - 1;
-    const int mbx = aa % g.wmb, mby = aa / g.wmb;
+    constexpr int DIAG = H264R_INTER_DIAG;
+    constexpr bool PK = (H264R_INTER_FAST & 1) != 0;
+    const Inter4Lane L = inter4_lane(g, a0, aend, lane);
     const h264r_slice* slices = b.slices + (size_t)pic * b.slice_stride;
-
-    // ---- MB record (inter4_pre: two 16-byte loads -- a struct copy becomes one byte load
-    // per field, each waited on its own) and the motion of this block
-    const int X4 = mbx * 4 + bx, Y4 = mby * 4 + by;
+    // MB record (inter4_pre: two 16-byte loads -- a struct copy becomes one byte load per field,
+    // each waited on its own), its slice header and the motion of this block
     const h264r_mb q = pre.q;
-    const h264r_slice* qs = &slices[q.slice];
     const uint2 qsh = slice_hdr(slices, S, q.slice);
     const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, q.slice, 0);
     const uint2 m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, q.slice, 1);
-    const int q_type = qsh.x & 255;
-    const int wp_mode = qsh.y & 255;
 
-    // ---- reconstruction of inter / I_PCM MBs (intra MBs: the lanes idle here)
-    [&]() {
-        const bool pcm = q.mb_type == H264R_I_PCM;
-        if (!valid || (mb_is_intra(q) && !pcm)) return;              // intra: k_intra_* (lanes idle here)
-        const bool sp_mb = q_type == H264R_SLICE_SP && !mb_is_intra(q);
-        if constexpr (!SP) {
-            if (sp_mb) { *sp_flag = tag; return; }                   // k_inter_sp's
-        } else {
-            if (!sp_mb) return;
-        }
-        const int16_t* lv = b.levels + q.coef_off;
-        // my 4x4 block in the MB-tiled reconstruction (device_common.h): rows of 16 / 8 bytes
-        uint8_t* const rmb = recon_mb(recon, g, pic, aa);
-        uint8_t* ydst = rmb + (by * 4) * 16 + bx * 4;
-        const int coff = RECON_CB + (by * 2) * 8 + bx * 2;          // Cb; Cr 64 bytes on
-        if (pcm) {                                                       // mb_pred_ipcm decoder.cc:149-168
-            const uint8_t* raw = reinterpret_cast<const uint8_t*>(lv);
-    #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<uint32_t*>(ydst + r * 16) =
-                    *reinterpret_cast<const uint32_t*>(raw + (by * 4 + r) * 16 + bx * 4);
-    #pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-    #pragma unroll
-                for (int r = 0; r < 2; ++r)
-                    *reinterpret_cast<uint16_t*>(rmb + coff + pl * 64 + r * 8) =
-                        *reinterpret_cast<const uint16_t*>(raw + 256 + pl * 64 + (by * 2 + r) * 8 + bx * 2);
-            return;
-        }
+    const bool pcm = q.mb_type == H264R_I_PCM;
+    if (!L.valid || (mb_is_intra(q) && !pcm)) return;                // intra: k_intra_* (lanes idle here)
+    if ((qsh.x & 255) == H264R_SLICE_SP && !mb_is_intra(q)) { *sp_flag = tag; return; }   // k_inter_sp's
+    if (pcm) { inter4_pcm(recon_mb(recon, g, pic, L.aa), L, b.levels + q.coef_off); return; }
 
-        // ---- residual inputs: issued after the motion compensation, so that they are not
-        // live across it (30 VGPRs: k_inter4r fits 128 VGPRs = 4 waves/SIMD; config 3
-        // 475 -> 493 M MB/s, profiles/r03_h_inter_ab.txt)
-        const int cbpl = q.cbp & 15, cbpc = q.cbp >> 4;
-        const int t8 = (q.flags & H264R_MBF_T8x8) != 0;
-        const h264r_quant* __restrict__ qt = &b.quant[pic];
-        const int qpl = q.qp_scaled[0];
-        const int b8 = (by >> 1) * 2 + (bx >> 1);
-        const int loff = b8_offset(q.cbp, b8);
-        uint4 lev[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-        uint4 lsc[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-        // chroma: my 2x2 quadrant of chroma 4x4 block cb of each plane + the plane's 4 DC levels
-        const int cb = (by >> 1) * 2 + (bx >> 1), cr = (by & 1) * 2, cc = (bx & 1) * 2;
-        uint32_t clev[2][2] = {{0, 0}, {0, 0}}, csc[2][2] = {{0, 0}, {0, 0}};
-        uint2 cdc[2] = {make_uint2(0, 0), make_uint2(0, 0)};
-        int cdcs[2] = {0, 0};
-        auto load_residual = [&]() {
-            if (loff >= 0) {
-                if (!t8) {                      // 4x4 block: 16 raster levels
-                    const uint4* p = reinterpret_cast<const uint4*>(lv + loff + ((by & 1) * 2 + (bx & 1)) * 16);
-                    lev[0] = p[0]; lev[1] = p[1];
-                    const uint4* s = reinterpret_cast<const uint4*>(&qt->scale4x4[1][0][qpl % 6][0]);
-                    lsc[0] = s[0]; lsc[1] = s[1];
-                } else {                        // my 4x4 quadrant of the 8x8 block: rows (by&1)*4.., cols (bx&1)*4..
-                    const int16_t* p = lv + loff + (by & 1) * 32 + (bx & 1) * 4;
-                    const int16_t* s = &qt->scale8x8[1][0][qpl % 6][(by & 1) * 32 + (bx & 1) * 4];
-                    const uint2 r0 = ld8(p), r1 = ld8(p + 8), r2 = ld8(p + 16), r3 = ld8(p + 24);
-                    lev[0] = make_uint4(r0.x, r0.y, r1.x, r1.y); lev[1] = make_uint4(r2.x, r2.y, r3.x, r3.y);
-                    const uint2 s0 = ld8(s), s1 = ld8(s + 8), s2 = ld8(s + 16), s3 = ld8(s + 24);
-                    lsc[0] = make_uint4(s0.x, s0.y, s1.x, s1.y); lsc[1] = make_uint4(s2.x, s2.y, s3.x, s3.y);
-                }
-            }
-            if (cbpc) {
-                const LevelOffs lo = level_offsets(q);
-    #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    const int qpc = q.qp_scaled[1 + pl];
-                    cdc[pl] = ld8(lv + lo.cdc + pl * 4);
-                    cdcs[pl] = qt->scale4x4[1][1 + pl][qpc % 6][0];
-                    if (cbpc == 2) {
-    #pragma unroll
-                        for (int r = 0; r < 2; ++r) {
-                            clev[pl][r] = *reinterpret_cast<const uint32_t*>(lv + lo.cac + pl * 64 + cb * 16 + (cr + r) * 4 + cc);
-                            csc[pl][r] = *reinterpret_cast<const uint32_t*>(&qt->scale4x4[1][1 + pl][qpc % 6][(cr + r) * 4 + cc]);
-                        }
-                    }
-                }
-            }
-        };
+    uint32_t predY[4], predC[2];
+    inter4_predict(b, g, pic, L, S, &slices[q.slice], qsh.y & 255, m0, m1, predY, predC);
+    // What only the residual and the stores read comes after the motion compensation, so that it is
+    // not live across it: the residual inputs (30 VGPRs: k_inter4r fits 128 VGPRs = 4 waves/SIMD;
+    // config 3 475 -> 493 M MB/s, profiles/r03_h_inter_ab.txt) and the two 64-bit addresses (formed
+    // before it, the kernel took 127 VGPRs instead of 125)
+    Inter4Res R = {};
+    if constexpr (!(DIAG & 16)) R = inter4_res_load(q, L, b.levels + q.coef_off, &b.quant[pic]);
+    uint8_t* const rmb = recon_mb(recon, g, pic, L.aa);
 
-        // ---- prediction
-        const int r0 = (int8_t)(m0.y & 255), r1 = (int8_t)(m1.y & 255);
-        const int dir = (r0 >= 0 && r1 >= 0) ? 2 : (r0 >= 0 ? 0 : 1);
-        // the prediction of each list in named registers: an array indexed by the (not
-        // unrolled) list loop was promoted to LDS by the compiler (48 B per lane)
-        uint32_t pY[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, pC[2][2] = {{0, 0}, {0, 0}};
-        // a field picture (include/h264r.h H264R_TOP_FIELD) reads fields of the DPB frames:
-        // every second row from the field's first row, clamped to the field's own rows
-        const int structure = (int)__builtin_amdgcn_readfirstlane(ld_const(&b.pics[pic].structure));
-        const int fld = structure != H264R_FRAME;
-    #pragma unroll 1
-        for (int l = 0; l < 2; ++l) {
-            const uint2 mw = l ? m1 : m0;
-            const int rr = l ? r1 : r0;
-            const bool use = rr >= 0;
-            if (!__any(use)) continue;                                  // P pictures: list 1 never
-            uint32_t tY[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
-            uint32_t tC[2] = {0x80808080u, 0x80808080u};                // no_ref: 128 (inter_prediction.cc:164-167,366-369)
-            const int ref = (int8_t)((mw.y >> 8) & 255);                // slot | H264R_REF_BOTTOM
-            const int slot = ref & 31, bot = fld & (ref >> 6);
-            const bool ok = use && ref >= 0 && (ref & ~H264R_REF_BOTTOM) < H264R_MAX_SLOTS && rr < H264R_MAX_REFS &&
-                            S.planes[slot * 3];
-            const int mvx = (int16_t)(mw.x & 0xFFFF), mvy = (int16_t)(mw.x >> 16);
-            const int vx = X4 * 16 + mvx, vy = Y4 * 16 + mvy;           // quarter luma / eighth chroma units
-            const int x = vx >> 2, y = vy >> 2;
-            {
-                // the 9 window rows of the lane's own block, straight from the plane
-                uint32_t w[9][3];
-#if H264R_INTER_DIAG & 4
-                // diagnostic build (wrong output): no window loads, no luma filter
-                (void)x; (void)y;
-                tY[0] = tY[1] = tY[2] = tY[3] = (uint32_t)(vx ^ vy);
-#elif H264R_INTER_DIAG & 2
-                // diagnostic build (wrong output): the window loads without the luma filter
-                if (ok) luma_window_global(S.planes[slot * 3] + bot * g.W, g.W, g.W << fld, g.H, x, y, w);
-                if (ok) { uint32_t acc = 0;
-    #pragma unroll
-                    for (int r = 0; r < 9; ++r) acc ^= w[r][0] ^ w[r][1] ^ w[r][2];
-                    tY[0] = tY[1] = tY[2] = tY[3] = acc; }
-#else
-                if (ok) luma_window_global(S.planes[slot * 3] + bot * g.W, g.W, g.W << fld, g.H, x, y, w);
-                if (ok) luma_block_pred(w, g.W, x, vx & 3, vy & 3, tY);
-#endif
-            }
-            // a reference field of the other parity: the chroma sample grid sits a quarter
-            // chroma row off (get_block_chroma inter_prediction.cc:352-355)
-            const int vyc = vy + (fld && bot != (structure == H264R_BOTTOM_FIELD) ? (bot ? -2 : 2) : 0);
-#if H264R_INTER_DIAG & 8
-            tC[0] = tC[1] = (uint32_t)vyc;        // diagnostic build (wrong output): no chroma MC
-#else
-            if (ok) chroma_block_pred2(S.planes[slot * 3 + 1] + bot * g.Wc, S.planes[slot * 3 + 2] + bot * g.Wc, g.Wc,
-                                       g.Wc << fld, g.Hc, vx >> 3, vyc >> 3, vx & 7, vyc & 7, tC);
-#endif
-            const bool l1 = l != 0;
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                pY[0][i] = (use && !l1) ? tY[i] : pY[0][i];
-                pY[1][i] = (use && l1) ? tY[i] : pY[1][i];
-            }
-    #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                pC[0][k] = (use && !l1) ? tC[k] : pC[0][k];
-                pC[1][k] = (use && l1) ? tC[k] : pC[1][k];
-            }
-        }
-        uint32_t predY[4], predC[2];
-        WpPar wpp[3] = {};
-        if (wp_mode != 0) {
-            const WpRaw wr = wp_raw(qs, r0, r1);
-    #pragma unroll
-            for (int pl = 0; pl < 3; ++pl) wpp[pl] = wp_params(wr, wp_mode, dir, pl);
-        }
-    #pragma unroll
-        for (int i = 0; i < 4; ++i) predY[i] = wp_combine4(wpp[0], wp_mode, dir, pY[0][i], pY[1][i]);
-    #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) predC[pl] = wp_combine4(wpp[1 + pl], wp_mode, dir, pC[0][pl], pC[1][pl]);
-#if !(H264R_INTER_DIAG & 16)
-        load_residual();
-#endif
+    s16x2 rp[4][2];
+    if constexpr (DIAG & (16 | 64)) luma_res_stub(R, rp);
+    else inter4_luma_residual<PK>(q, L, R, rp);
+    if constexpr (DIAG & 1) inter4_store_luma_16b(rmb, L, predY, rp);
+    else inter4_store_luma(rmb, L, predY, rp);
 
-        if constexpr (SP) {
-            // ---- itrans_sp of this lane's 4x4 block (:1132-1187): the prediction is
-            // transformed, combined with the level and re-quantised at QsY; the
-            // reconstruction is the clipped inverse transform alone
-            const int qp = q.qp_y, qsy = qs->qs_y, sw = qs->sp_switch;
-            const int per = qpl / 6;
-            int cf[4][4];
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int p0 = predY[i] & 255, p1 = (predY[i] >> 8) & 255, p2 = (predY[i] >> 16) & 255, p3 = predY[i] >> 24;
-                fwd4(p0, p1, p2, p3, cf[i][0], cf[i][1], cf[i][2], cf[i][3]);
-            }
-    #pragma unroll
-            for (int c = 0; c < 4; ++c) fwd4(cf[0][c], cf[1][c], cf[2][c], cf[3][c], cf[0][c], cf[1][c], cf[2][c], cf[3][c]);
-    #pragma unroll
-            for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const uint4 lw = lev[i >> 1], sw4 = lsc[i >> 1];
-                    const uint32_t lo_ = (i & 1) ? lw.z : lw.x, hi_ = (i & 1) ? lw.w : lw.y;
-                    const uint32_t slo = (i & 1) ? sw4.z : sw4.x, shi = (i & 1) ? sw4.w : sw4.y;
-                    const int cr = dq4(sel16(lo_, hi_, c), sel16(slo, shi, c), per);   // inverse_quantize :409-413
-                    cf[i][c] = sp_luma_coef(cr, cf[i][c], i, c, qp, qsy, sw);
-                }
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) idct4_inplace(cf[i][0], cf[i][1], cf[i][2], cf[i][3]);
-    #pragma unroll
-            for (int c = 0; c < 4; ++c) idct4_inplace(cf[0][c], cf[1][c], cf[2][c], cf[3][c]);
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uint32_t wv = 0;
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int v = (cf[i][c] + 32) >> 6;
-                    // opaque: shift + clamp + byte packing otherwise becomes v_ashr_pk_u8_i32, whose
-                    // upper result half the compiler takes as zero -- on MI355X it kept the old
-                    // register's upper bits (bytes 2-3 = 0xFF after a negative input), measured
-                    asm volatile("" : "+v"(v));
-                    wv |= (uint32_t)clip255(v) << (8 * c);
-                }
-                *reinterpret_cast<uint32_t*>(ydst + i * 16) = wv;
-            }
-            // ---- itrans_sp_cr (:1190-1265) then inverse_transform_chroma (:1033-1049):
-            // chroma block cb is spread over lanes {blk, ^1, ^4, ^5}; my 2x2 quadrant
-            // (rows cr.., cols cc..).  The DC pass takes the raw DC levels (transform_chroma_dc
-            // skips SP inter MBs, :865-875), the AC pass the PREDICTION SAMPLES (:1246)
-    #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                const int qpc = q.qp_c[pl], qsc = qs->qs_c[pl];
-                int pr[2][2], f[2][2];
-    #pragma unroll
-                for (int r = 0; r < 2; ++r)
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) pr[r][c] = (predC[pl] >> (16 * r + 8 * c)) & 255;
-                // forward transform: rows (my 2 columns + the 2 of lane ^ 1), then columns
-                // (my 2 rows + the 2 of lane ^ 4)
-                int t[2][2];
-    #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const int o0 = lane_xor1(pr[r][0]), o1 = lane_xor1(pr[r][1]);
-                    const int q0 = cc ? o0 : pr[r][0], q1 = cc ? o1 : pr[r][1], q2 = cc ? pr[r][0] : o0, q3 = cc ? pr[r][1] : o1;
-                    int y0, y1, y2, y3;
-                    fwd4(q0, q1, q2, q3, y0, y1, y2, y3);
-                    t[r][0] = cc ? y2 : y0;
-                    t[r][1] = cc ? y3 : y1;
-                }
-    #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int o0 = lane_xor4(t[0][c]), o1 = lane_xor4(t[1][c]);
-                    const int q0 = cr ? o0 : t[0][c], q1 = cr ? o1 : t[1][c], q2 = cr ? t[0][c] : o0, q3 = cr ? t[1][c] : o1;
-                    int y0, y1, y2, y3;
-                    fwd4(q0, q1, q2, q3, y0, y1, y2, y3);
-                    f[0][c] = cr ? y2 : y0;
-                    f[1][c] = cr ? y3 : y1;
-                }
-                // the four blocks' DC coefficients (lanes 0, 2, 8, 10 of the MB's 16)
-                const int gb = lane & ~15;
-                const int d00 = __shfl(f[0][0], gb + 0), d01 = __shfl(f[0][0], gb + 2);
-                const int d10 = __shfl(f[0][0], gb + 8), d11 = __shfl(f[0][0], gb + 10);
-                int mp[4] = {d00 + d10 + d01 + d11, d00 - d10 + d01 - d11, d00 + d10 - d01 - d11, d00 - d10 - d01 + d11};
-                const int c00 = (int16_t)(cdc[pl].x & 0xFFFF), c01 = (int16_t)(cdc[pl].x >> 16);
-                const int c10 = (int16_t)(cdc[pl].y & 0xFFFF), c11 = (int16_t)(cdc[pl].y >> 16);
-                const int crd[4] = {c00, c01, c10, c11};
-                const int ls0 = sp_ls2(qsc % 6, 0, 0);
-    #pragma unroll
-                for (int n = 0; n < 4; ++n) {
-                    const int cp = mp[n];
-                    int cij;
-                    if (qs->sp_switch) {
-                        cij = ((sp_sgn(cp) * (iabs(cp) * ls0 + (1 << (15 + qsc / 6)))) >> (16 + qsc / 6)) + cp;
-                    } else {
-                        const int cs = cp + ((int)((unsigned)(crd[n] * sp_dq(qpc % 6, 0, 0) * 16) << (qpc / 6)) >> 9);
-                        cij = (sp_sgn(cs) * (iabs(cs) * ls0 + (1 << (15 + qsc / 6)))) >> (16 + qsc / 6);
-                    }
-                    mp[n] = (int)((unsigned)(cij * sp_dq(qsc % 6, 0, 0)) << (qpc / 6));
-                }
-                // AC (every position; (0,0) is replaced by the DC result below)
-                int k[2][2];
-    #pragma unroll
-                for (int r = 0; r < 2; ++r)
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const int j = cr + r, i = cc + c;
-                        const int crv = dq4((int16_t)(clev[pl][r] >> (16 * c)), (int16_t)(csc[pl][r] >> (16 * c)), qpc / 6);
-                        const int cp = pr[r][c], ls = sp_ls2(qsc % 6, j, i);
-                        int cij;
-                        if (qs->sp_switch) {
-                            cij = crv + ((sp_sgn(cp) * (iabs(cp) * ls + (1 << (14 + qsc / 6)))) >> (15 + qsc / 6));
-                        } else {
-                            const int cs = cp + ((int)((unsigned)(crv * sp_dq(qpc % 6, j, i) * SP_A[j * 4 + i]) << (qpc / 6)) >> 9);
-                            cij = (sp_sgn(cs) * (iabs(cs) * ls + (1 << (14 + qsc / 6)))) >> (15 + qsc / 6);
-                        }
-                        k[r][c] = (int)((unsigned)(cij * sp_dq(qsc % 6, j, i)) << (qpc / 6));
-                    }
-                if (cr == 0 && cc == 0) {
-                    const int dcv = cb == 0 ? (mp[0] + mp[1] + mp[2] + mp[3]) >> 1
-                                  : cb == 1 ? (mp[0] + mp[1] - mp[2] - mp[3]) >> 1
-                                  : cb == 2 ? (mp[0] - mp[1] + mp[2] - mp[3]) >> 1
-                                            : (mp[0] - mp[1] - mp[2] + mp[3]) >> 1;
-                    k[0][0] = dcv;
-                }
-                // inverse transform (as below) and construction with the prediction
-                int rcv[2][2];
-                {
-                    int tt[2][2];
-    #pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        const int o0 = lane_xor1(k[r][0]), o1 = lane_xor1(k[r][1]);
-                        const int d0 = cc ? o0 : k[r][0], d1 = cc ? o1 : k[r][1], d2 = cc ? k[r][0] : o0, d3 = cc ? k[r][1] : o1;
-                        int y0, y1, y2, y3;
-                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                        tt[r][0] = cc ? y2 : y0;
-                        tt[r][1] = cc ? y3 : y1;
-                    }
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        const int o0 = lane_xor4(tt[0][c]), o1 = lane_xor4(tt[1][c]);
-                        const int d0 = cr ? o0 : tt[0][c], d1 = cr ? o1 : tt[1][c], d2 = cr ? tt[0][c] : o0, d3 = cr ? tt[1][c] : o1;
-                        int y0, y1, y2, y3;
-                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                        rcv[0][c] = ((cr ? y2 : y0) + 32) >> 6;
-                        rcv[1][c] = ((cr ? y3 : y1) + 32) >> 6;
-                    }
-                }
-                uint8_t* cdst = rmb + coff + pl * 64;
-    #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const uint32_t wv = (uint32_t)clip255(pr[r][0] + rcv[r][0]) | ((uint32_t)clip255(pr[r][1] + rcv[r][1]) << 8);
-                    *reinterpret_cast<uint16_t*>(cdst + r * 8) = (uint16_t)wv;
-                }
-            }
-            return;
-        }
-        // ---- luma residual (transform.cc:1058-1073): rp[i][h] = {row i's columns 2h, 2h + 1} as a
-        // 16-bit pair, what the construction takes (construct4)
-        s16x2 rp[4][2];
-    #pragma unroll
-        for (int i = 0; i < 4; ++i) rp[i][0] = rp[i][1] = splat16(0);
-        // the 32-bit paths' result, saturated (pk_sat)
-        auto pack_res = [&](const int (&res)[4][4]) {
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                rp[i][0] = pk_sat(res[i][0], res[i][1]);
-                rp[i][1] = pk_sat(res[i][2], res[i][3]);
-            }
-        };
-        const bool byp = (q.flags & H264R_MBF_BYPASS) != 0;
-#if H264R_INTER_DIAG & 64
-        // diagnostic build (wrong output): the luma levels loaded, not transformed
-        rp[0][0].x = (short)((lev[0].x ^ lev[0].y ^ lev[0].z ^ lev[0].w ^ lev[1].x ^ lev[1].y ^ lev[1].z ^ lev[1].w ^
-                              lsc[0].x ^ lsc[1].y) & 3);
-#endif
-        if (!(H264R_INTER_DIAG & (16 | 64)) && __any(cbpl != 0)) {
-            const int per = qpl / 6;
-            // dq4 / dq8 (transform.cc:394-419) as one form, rounding and shift per lane: the
-            // lanes of a wave mix 4x4 and 8x8 MBs, and a select per value (not a branch) keeps
-            // the 16 values free of exec-mask work
-            const int drnd = t8 ? 32 : 8, dsh = t8 ? 6 : 4;
-            auto level_at = [&](int i, int c) {
-                const uint4 lw = lev[i >> 1];
-                return sel16((i & 1) ? lw.z : lw.x, (i & 1) ? lw.w : lw.y, c);
-            };
-            auto scale_at = [&](int i, int c) {
-                const uint4 sw = lsc[i >> 1];
-                return sel16((i & 1) ? sw.z : sw.x, (i & 1) ? sw.w : sw.y, c);
-            };
-            // (each branch below dequantises for itself: the lossless one takes the levels, the 4x4
-            // one a biased form its range test reads)
-            int d[4][4];
-            auto dequant = [&]() {
-    #pragma unroll
-                for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const int lvv = level_at(i, c), scv = scale_at(i, c);
-                        const int dqv = ((lvv * scv) * (1 << per) + drnd) >> dsh;
-                        d[i][c] = byp ? lvv : dqv;
-                    }
-            };
-            // lossless MBs (TransformBypassModeFlag): the levels are the residual, DPCM'd in
-            // place down the columns / along the rows when the block's Intra4x4PredMode /
-            // Intra8x8PredMode is vertical / horizontal (bypass_4x4 / bypass_8x8
-            // transform.cc:736-778; inverse_transform_4x4 / _8x8 :986-1016 read those modes
-            // for inter MBs too: whatever the parser's mb_t slot holds).  The flag is
-            // uniform over an MB's 16 lanes, so the cross-lane carries stay inside the branch.
-            if (byp) {
-                dequant();
-                const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
-                const uint64_t ipw = (uint64_t)qw[5] | ((uint64_t)qw[6] << 32);
-                const int bk = t8 ? b8 : (by >> 1) * 8 + (bx >> 1) * 4 + (by & 1) * 2 + (bx & 1);
-                const int mode = (int)((ipw >> (4 * bk)) & 15);
-                const bool vert = mode == 0, horz = mode == 1;
-    #pragma unroll
-                for (int i = 1; i < 4; ++i)
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) d[i][c] += vert ? d[i - 1][c] : 0;
-    #pragma unroll
-                for (int c = 1; c < 4; ++c)
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i][c] += horz ? d[i][c - 1] : 0;
-                // 8x8: the quadrant above (lane ^ 4) / to the left (lane ^ 1) carries in
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int up = lane_xor4(d[3][c]);
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) d[i][c] += (t8 && vert && (by & 1)) ? up : 0;
-                }
-    #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int left = lane_xor1(d[i][3]);
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) d[i][c] += (t8 && horz && (bx & 1)) ? left : 0;
-                }
-                pack_res(d);
-            } else
-            if (!__any(t8 != 0)) {
-                // 4x4, all in-lane.  On 16-bit pairs when every lane's block passes PK_RES_MAX (real
-                // content does): rows 0, 1 and rows 2, 3 as the halves of two transforms, a 2x2
-                // transpose of the pairs, then columns {0, 1} and {2, 3}
-                bool pk = (H264R_INTER_FAST & 1) != 0;
-                uint32_t u[4][4];
-                if (pk) {
-                    uint32_t gs = 0;
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            u[i][c] = dq4_biased(level_at(i, c), scale_at(i, c), per);
-                            gs = abs_acc_biased(u[i][c], gs);
-                        }
-                    pk = !__any(gs > PK_RES_MAX);
-                }
-                if (pk) {
-                    s16x2 A[4], B[4];
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        A[c] = pk_lo(u[0][c], u[1][c]);
-                        B[c] = pk_lo(u[2][c], u[3][c]);
-                    }
-                    A[0] += (s16x2){32, 0};
-                    idct4_pk(A[0], A[1], A[2], A[3]);
-                    idct4_pk(B[0], B[1], B[2], B[3]);
-    #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        s16x2 x0 = pk_lo(as_u32(A[2 * h]), as_u32(A[2 * h + 1])), x1 = pk_hi(as_u32(A[2 * h]), as_u32(A[2 * h + 1]));
-                        s16x2 x2 = pk_lo(as_u32(B[2 * h]), as_u32(B[2 * h + 1])), x3 = pk_hi(as_u32(B[2 * h]), as_u32(B[2 * h + 1]));
-                        idct4_pk(x0, x1, x2, x3);
-                        rp[0][h] = x0 >> splat16(6); rp[1][h] = x1 >> splat16(6);
-                        rp[2][h] = x2 >> splat16(6); rp[3][h] = x3 >> splat16(6);
-                    }
-                } else {
-                    // rows then columns, 32-bit (the biased values are the dequantised ones + 2^27,
-                    // exactly: taken back, not computed again, so that the range test keeps its
-                    // own shift-and-add)
-                    if (H264R_INTER_FAST & 1) {
-    #pragma unroll
-                        for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                            for (int c = 0; c < 4; ++c) d[i][c] = (int)(u[i][c] - DQ4_BIAS);
-                    } else {
-                        dequant();
-                    }
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) idct4_inplace(d[i][0], d[i][1], d[i][2], d[i][3]);
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) idct4_inplace(d[0][c], d[1][c], d[2][c], d[3][c]);
-                    int res[4][4];
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                        for (int c = 0; c < 4; ++c) res[i][c] = (d[i][c] + 32) >> 6;
-                    pack_res(res);
-                }
-            } else {
-                // 8x8 (only t8 MBs reach here with d != 0 for their lanes; 4x4 MBs of the same
-                // wave take the in-lane path below).  Rows: my 4 + the 4 of lane ^ 1.
-                dequant();
-                int e4[4][4], res[4][4];
-    #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    int in[8], outv[8];
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const int ov = lane_xor1(d[i][c]);
-                        in[c] = (bx & 1) ? ov : d[i][c];
-                        in[4 + c] = (bx & 1) ? d[i][c] : ov;
-                    }
-                    idct8(in, outv);
-                    // mask select: a ternary over the two halves became a lane-indexed array
-                    // read, which the compiler placed in LDS (32 B per lane)
-                    const int mx = -(bx & 1);
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) e4[i][c] = (outv[c] & ~mx) | (outv[4 + c] & mx);
-                }
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    int in[8], outv[8];
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        in[i] = lane_lo4(e4[i][c]);         // rows 0..3: the lane with by even
-                        in[4 + i] = lane_hi4(e4[i][c]);
-                    }
-                    idct8(in, outv);
-                    const int my = -(by & 1);
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) res[i][c] = t8 ? ((outv[i] & ~my) | (outv[4 + i] & my)) : 0;
-                }
-                if (!t8) {
-    #pragma unroll
-                    for (int i = 0; i < 4; ++i) idct4_inplace(d[i][0], d[i][1], d[i][2], d[i][3]);
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) idct4_inplace(d[0][c], d[1][c], d[2][c], d[3][c]);
-                }
-    #pragma unroll
-                for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) res[i][c] = ((t8 ? res[i][c] : d[i][c]) + 32) >> 6;
-                pack_res(res);
-            }
-        }
-        // ---- construction + store, luma
-#if H264R_INTER_DIAG & 1
-        {   // diagnostic build (wrong output): one 16-byte store per lane, an MB's 16 lanes contiguous
-            uint32_t wv4[4];
-    #pragma unroll
-            for (int i = 0; i < 4; ++i) wv4[i] = construct4(predY[i], rp[i][0], rp[i][1]);
-            *reinterpret_cast<uint4*>(rmb + blk * 16) = make_uint4(wv4[0], wv4[1], wv4[2], wv4[3]);
-        }
-#else
-    #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<uint32_t*>(ydst + i * 16) = construct4(predY[i], rp[i][0], rp[i][1]);
-#endif
-
-        // ---- chroma residual (transform.cc:1081-1091, DC :875-889): chroma block cb is
-        // spread over lanes {blk, ^1, ^4, ^5}; my quadrant rows cr.., cols cc..
-        // rcp[pl][r] = {row r's two samples of plane pl} as a 16-bit pair
-        s16x2 rcp[2][2] = {{splat16(0), splat16(0)}, {splat16(0), splat16(0)}};
-#if H264R_INTER_DIAG & 128
-        // diagnostic build (wrong output): the chroma levels loaded, not transformed
-    #pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-            rcp[pl][0].x = (short)((clev[pl][0] ^ clev[pl][1] ^ csc[pl][0] ^ csc[pl][1] ^ cdc[pl].x ^ cdc[pl].y ^ (uint32_t)cdcs[pl]) & 3);
-#endif
-        if (!(H264R_INTER_DIAG & (16 | 128)) && __any(cbpc != 0)) {
-            const bool dcl_lane = cr == 0 && cc == 0;
-            // k: the dequantised coefficients + DQ4_BIAS (dq4_biased), the scaled DC among them
-            uint32_t k[2][2][2];
-            int dcl[2];
-    #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) {
-                const int qpc = q.qp_scaled[1 + pl], per = qpc / 6;
-    #pragma unroll
-                for (int r = 0; r < 2; ++r)
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c)
-                        k[pl][r][c] = dq4_biased((int16_t)(clev[pl][r] >> (16 * c)), (int16_t)(csc[pl][r] >> (16 * c)), per);
-                const int c00 = (int16_t)(cdc[pl].x & 0xFFFF), c01 = (int16_t)(cdc[pl].x >> 16);
-                const int c10 = (int16_t)(cdc[pl].y & 0xFFFF), c11 = (int16_t)(cdc[pl].y >> 16);
-                const int e00 = c00 + c01, e01 = c00 - c01, e10 = c10 + c11, e11 = c10 - c11;
-                // f = (e00 or e01) +/- (e10 or e11) by cb's bits: arithmetic, not a branch tree
-                const int ea = (cb & 1) ? e01 : e00, eb = (cb & 1) ? e11 : e10;
-                const int f = ea + (eb ^ -(cb >> 1)) + (cb >> 1);
-                if (dcl_lane) k[pl][0][0] = (uint32_t)(cbpc ? ((f * cdcs[pl]) * (1 << per)) >> 5 : 0) + DQ4_BIAS;
-                dcl[pl] = cb == 0 ? c00 : cb == 1 ? c01 : cb == 2 ? c10 : c11;
-            }
-            // Both planes at once as {Cb, Cr} pairs when every block of the wave passes PK_RES_MAX
-            // in both planes (the scaled DC included; lossless MBs do not use the transform).  A
-            // block's sum is over its four lanes, of the larger of the lane's two plane sums: never
-            // below either plane's own.  (|k| <= 2^27: no wrap.)
-            bool pk = (H264R_INTER_FAST & 1) != 0;
-            if (pk) {
-                uint32_t gs[2];
-    #pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    gs[pl] = abs_acc_biased(k[pl][0][0], abs_acc_biased(k[pl][0][1], abs_acc_biased(k[pl][1][0], abs_acc_biased(k[pl][1][1], 0))));
-                int m = byp ? 0 : (int)max(gs[0], gs[1]);
-                int o = lane_xor1(m);
-                asm volatile("" : "+v"(o));              // a move, not a fold into the add (tests/test_isa.py)
-                m = (int)((uint32_t)m + (uint32_t)o);
-                int lo = lane_lo4(m), hi = lane_hi4(m);
-                asm volatile("" : "+v"(lo), "+v"(hi));
-                pk = !__any((uint32_t)lo + (uint32_t)hi > PK_RES_MAX);
-            }
-            if (pk) {
-                s16x2 K[2][2];
-    #pragma unroll
-                for (int r = 0; r < 2; ++r)
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) K[r][c] = pk_lo(k[0][r][c], k[1][r][c]);
-                K[0][0] += splat16(dcl_lane ? 32 : 0);   // the rounding, on both planes' DC
-                // rows: my 2 columns + the 2 of lane ^ 1
-                s16x2 t[2][2];
-    #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const s16x2 o0 = as_s16x2((uint32_t)lane_xor1((int)as_u32(K[r][0]))), o1 = as_s16x2((uint32_t)lane_xor1((int)as_u32(K[r][1])));
-                    s16x2 d0 = cc ? o0 : K[r][0], d1 = cc ? o1 : K[r][1], d2 = cc ? K[r][0] : o0, d3 = cc ? K[r][1] : o1;
-                    idct4_pk(d0, d1, d2, d3);
-                    t[r][0] = cc ? d2 : d0;
-                    t[r][1] = cc ? d3 : d1;
-                }
-                // columns: my 2 rows + the 2 of lane ^ 4
-                s16x2 rc2[2][2];
-    #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int t0 = (int)as_u32(t[0][c]), t1 = (int)as_u32(t[1][c]);
-                    s16x2 d0 = as_s16x2((uint32_t)lane_lo4(t0)), d1 = as_s16x2((uint32_t)lane_lo4(t1));
-                    s16x2 d2 = as_s16x2((uint32_t)lane_hi4(t0)), d3 = as_s16x2((uint32_t)lane_hi4(t1));
-                    idct4_pk(d0, d1, d2, d3);
-                    rc2[0][c] = (cr ? d2 : d0) >> splat16(6);
-                    rc2[1][c] = (cr ? d3 : d1) >> splat16(6);
-                }
-    #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    rcp[0][r] = pk_lo(as_u32(rc2[r][0]), as_u32(rc2[r][1]));
-                    rcp[1][r] = pk_hi(as_u32(rc2[r][0]), as_u32(rc2[r][1]));
-                }
-            } else {
-    #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    // rows: my 2 columns + the 2 of lane ^ 1
-                    int t[2][2], rc[2][2];
-    #pragma unroll
-                    for (int r = 0; r < 2; ++r) {
-                        const int k0 = (int)(k[pl][r][0] - DQ4_BIAS), k1 = (int)(k[pl][r][1] - DQ4_BIAS);
-                        const int o0 = lane_xor1(k0), o1 = lane_xor1(k1);
-                        const int d0 = cc ? o0 : k0, d1 = cc ? o1 : k1, d2 = cc ? k0 : o0, d3 = cc ? k1 : o1;
-                        int y0, y1, y2, y3;
-                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                        t[r][0] = cc ? y2 : y0;
-                        t[r][1] = cc ? y3 : y1;
-                    }
-                    // columns: my 2 rows + the 2 of lane ^ 4
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        // (rows 0..1 from the lane with by even, 2..3 from the other)
-                        const int d0 = lane_lo4(t[0][c]), d1 = lane_lo4(t[1][c]), d2 = lane_hi4(t[0][c]), d3 = lane_hi4(t[1][c]);
-                        int y0, y1, y2, y3;
-                        idct4(d0, d1, d2, d3, y0, y1, y2, y3);
-                        rc[0][c] = ((cr ? y2 : y0) + 32) >> 6;
-                        rc[1][c] = ((cr ? y3 : y1) + 32) >> 6;
-                    }
-                    rcp[pl][0] = pk_sat(rc[0][0], rc[0][1]);
-                    rcp[pl][1] = pk_sat(rc[1][0], rc[1][1]);
-                }
-            }
-            // lossless: the raw levels, DC at (0,0) (transform.cc:453-455,860); an inter MB's
-            // intra_chroma_pred_mode is DC (macroblock_t::init slice_data.cc:482), so
-            // bypass_chroma (:802-822) copies.  A row's two levels are its loaded word.
-            if (byp) {
-    #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) {
-                    rcp[pl][0] = dcl_lane ? pk_hi((uint32_t)dcl[pl] << 16, clev[pl][0]) : as_s16x2(clev[pl][0]);
-                    rcp[pl][1] = as_s16x2(clev[pl][1]);
-                }
-            }
-        }
-    #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-            uint8_t* cdst = rmb + coff + pl * 64;
-    #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const s16x2 pr = as_s16x2(__builtin_amdgcn_perm(0, predC[pl], r ? 0x0c030c02u : 0x0c010c00u));
-                const s16x2 sv = pk_clip255(__builtin_elementwise_add_sat(pr, rcp[pl][r]));
-                *reinterpret_cast<uint16_t*>(cdst + r * 8) = (uint16_t)__builtin_amdgcn_perm(0, as_u32(sv), 0x0c0c0200u);
-            }
-        }
-    }();
+    s16x2 rcp[2][2];
+    if constexpr (DIAG & (16 | 128)) chroma_res_stub(R, rcp);
+    else inter4_chroma_residual<PK>(q, L, R, rcp);
+    inter4_store_chroma(rmb, L, predC, rcp);
 }
 
 }  // namespace h264r
+

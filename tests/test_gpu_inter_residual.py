@@ -81,7 +81,7 @@ def _dq4(lev, scale, per):
 def _wave_paths(p, quant):
     """Per wave of k_inter4r (four consecutive MBs of the picture) which residual path its luma and
     its chroma take: 'packed', 'fallback' or None (no coded residual, or a path without the test).
-    Mirrors inter4_mbs<false>: the lanes of intra, PCM and lossless MBs take no part in the test."""
+    Mirrors luma_res_4x4 / inter4_chroma_residual: the lanes of intra, PCM and lossless MBs take no part in the test."""
     s4 = quant["scale4x4"]
     out = []
     nmb = len(p.mbs)

@@ -78,6 +78,20 @@ def test_lane_lo4_hi4_stay_moves(forms):
     assert all(op == "v_mov_b32_dpp" for _, op in banked), banked
 
 
+def test_inter_kernels_register_budget():
+    """k_inter4r asks for 4 waves per SIMD (__launch_bounds__(256, H264R_INTER_WAVES), DESIGN.md section
+    3): 512 VGPRs per SIMD over 4 waves is 128 each, with nothing spilled and no scratch.  k_inter_sp
+    has no scratch either."""
+    if not os.path.exists(LIB):
+        pytest.skip("libh264r.so not built (__graft_entry__.build())")
+    res = isa_dpp.kernel_resources(LIB)
+    r4, sp = res["k_inter4r"], res["k_inter_sp"]
+    print("k_inter4r", r4, "k_inter_sp", sp)
+    assert r4["vgpr_count"] <= 128, r4
+    assert r4["vgpr_spill_count"] == 0 and r4["private_segment_fixed_size"] == 0, r4
+    assert sp["vgpr_spill_count"] == 0 and sp["private_segment_fixed_size"] == 0, sp
+
+
 def test_no_dpp_on_a_reversed_opcode(forms):
     """v_*rev*_dpp (subrev, lshlrev, lshrrev, ashrrev, ...): MI355X applies the lane select to src1."""
     bad = sorted({(k, op, m) for (k, op, m) in forms if "rev_" in op})
