@@ -1154,11 +1154,11 @@ int h264r_picture_end_async(h264r_ctx* c, int keep_slot)
     const int mbaff = P.h_pic.structure == H264R_MBAFF_FRAME;
     if (P.h_pic.structure < H264R_FRAME || P.h_pic.structure > H264R_MBAFF_FRAME) return H264R_EINVAL;
     if (mbaff) {
-        // MBAFF (include/h264r.h): 4:2:0, MB pairs, no SP slices, lossless MBs or implicit weights
+        // MBAFF (include/h264r.h): 4:2:0, MB pairs, no implicit weights (k_mbaff_inter flags the
+        // same cases, and an SP slice's 8x8 transforms and QsC >= 6, on the device: h264r_picture_wait)
         if (P.ph & 1) return H264R_EINVAL;
         for (const h264r_slice& sl : P.h_slices)
-            if (sl.slice_type == H264R_SLICE_SP || sl.wp_mode == 2) return H264R_EUNSUPPORTED;
-        for (const h264r_mb& m : P.h_mbs) if (m.flags & H264R_MBF_BYPASS) return H264R_EUNSUPPORTED;
+            if (sl.wp_mode == 2) return H264R_EUNSUPPORTED;
         for (size_t a = 0; a < P.h_mbs.size(); a += 1) {
             const size_t top = ((a / P.pw) & ~(size_t)1) * P.pw + a % P.pw;
             if ((P.h_mbs[a].flags ^ P.h_mbs[top].flags) & H264R_MBF_FIELD) return H264R_EINVAL;   // one flag per pair

@@ -8,7 +8,8 @@
 // of the frame and the MB holding it.  These kernels write the frame as it is after MbAffPostProc
 // and address it geometrically (H/ = R/src/codec/h264/):
 //
-//   k_mbaff_inter    one workgroup per MB, every MB of every picture at once: I_PCM and inter MBs
+//   k_mbaff_inter    one workgroup per MB, every MB of every picture at once: the refusals
+//                    (below), then I_PCM and inter MBs
 //                    (residual + motion compensation; a field MB predicts from the FIELDS of its
 //                    list's frames, get_ref_pic dpb.cc:1046-1055, with field block rows and the
 //                    chroma parity offset, inter_prediction.cc:356-361,470-474).
@@ -27,9 +28,18 @@
 //                    MB-order walk sees.
 //
 // This is the MBAFF format's own launch sequence: the frame / field-picture path (k_inter4r,
-// k_intra_levels, k_deblock2) keeps its layout.  4:2:0 only; no SP slices, lossless MBs or
-// implicit weights (the host refuses them).
+// k_intra_levels, k_deblock2) keeps its layout.  4:2:0 only.
+//
+// Lossless MBs (H264R_MBF_BYPASS: mb_residual takes the levels as the residual and accumulates them
+// along the block's prediction direction) and SP slices (mb_sp: inverse_transform_sp on the MB's
+// field or frame prediction; intra MBs as usual; an SP MB counts as intra for bS) are decoded; the
+// CPU oracle refuses both in MBAFF frames, so tests/golden/mbaff_ext.json pins them to the
+// reference itself.  Not decoded: implicit weights, SI, an SP slice's 8x8 transforms or QsC >= 6,
+// a pair whose MBs disagree on the field flag, a picture that is no MBAFF frame.  k_mbaff_inter
+// sets the context's error word for each of them (h264r_check reports it): a device-resident
+// batch reaches no host check.
 #include "device_common.h"
+#include "sp_math.h"
 
 namespace h264r {
 namespace {
@@ -112,14 +122,11 @@ DEV void idct8_1d(const int in[8], int out[8])                  // transform.cc:
     out[4] = f6 - f1; out[5] = f4 - f3; out[6] = f2 - f5; out[7] = f0 - f7;
 }
 
-// coeff_* + inverse_quantize, transform_luma_dc / transform_chroma_dc, inverse_4x4 / inverse_8x8
-// (transform.cc:394-456, 460-733, 825-910) of one 4:2:0 MB: R.cof holds its residual on return.
-// Blocks the cbp leaves uncoded have zero coefficients, so their residual is zero and
-// clip(residual + prediction) is the prediction (construction transform.cc:913-984).
-DEV void mb_residual(const h264r_mb& m, const int16_t* lv, const h264r_quant& q, ResLds& R, int t)
+// coeff_* + inverse_quantize, transform_luma_dc / transform_chroma_dc (transform.cc:394-456, 460-554,
+// 825-910) of one 4:2:0 MB into the zeroed R.cof.  sp: an inter MB of an SP slice, whose chroma DC
+// levels stay raw (transform_chroma_dc skips them, :865-875; mb_sp reads them from the level block).
+DEV void mb_coefs(const h264r_mb& m, const int16_t* lv, const h264r_quant& q, ResLds& R, int t, bool sp)
 {
-    for (int k = t; k < 3 * 256; k += 256) (&R.cof[0][0])[k] = 0;
-    __syncthreads();
     const int cbpl = m.cbp & 15, cbpc = m.cbp >> 4;
     const int inter = (m.flags & H264R_MBF_INTRA) ? 0 : 1;
     const bool t8 = (m.flags & H264R_MBF_T8x8) != 0, i16 = m.mb_type == H264R_I_16x16;
@@ -172,13 +179,18 @@ DEV void mb_residual(const h264r_mb& m, const int16_t* lv, const h264r_quant& q,
                                                           : (f[i] * scale + (1 << (5 - qP / 6))) >> (6 - qP / 6);
         }
     }
-    if ((t == 201 || t == 202) && cbpc) {                              // chroma DC (transform.cc:460-481, 858-889)
+    if ((t == 201 || t == 202) && cbpc && !sp) {                       // chroma DC (transform.cc:460-481, 858-889)
         const int pl = t - 200, qP = m.qp_scaled[pl], scale = q.scale4x4[inter][pl][qP % 6][0];
         const int16_t* c = cdc + (pl - 1) * 4;
         const int f[4] = {c[0] + c[1] + c[2] + c[3], c[0] - c[1] + c[2] - c[3], c[0] + c[1] - c[2] - c[3], c[0] - c[1] - c[2] + c[3]};
         for (int k = 0; k < 4; ++k) R.cof[pl][((k >> 1) * 4) * 8 + (k & 1) * 4] = ((f[k] * scale) * (1 << (qP / 6))) >> 5;
     }
-    __syncthreads();
+}
+
+// inverse_4x4 / inverse_8x8 (transform.cc:556-733) of the coefficients in R.cof, in place: the
+// luma plane (16 4x4 or 4 8x8 blocks) and the chroma planes' four 4x4 blocks each
+DEV void mb_itrans(bool t8, ResLds& R, int t)
+{
     // row passes
     if (t8) {
         if (t < 32) {
@@ -233,6 +245,144 @@ DEV void mb_residual(const h264r_mb& m, const int16_t* lv, const h264r_quant& q,
         R.cof[pl][(y0 + 3) * 8 + x0 + j] = (g0 - g3 + 32) >> 6;
     }
     __syncthreads();
+}
+
+// The levels of a TransformBypassModeFlag MB at their positions in the zeroed R.cof: they are the
+// residual before its DPCM (coeff_luma_ac / coeff_chroma_ac skip inverse_quantize, transform.cc:
+// 439-441,453-455; transform_luma_dc / transform_chroma_dc do nothing, :827,860), DC levels at the
+// (0, 0) of their 4x4 blocks.
+DEV void mb_bypass_levels(const h264r_mb& m, const int16_t* lv, ResLds& R, int t)
+{
+    const int cbpl = m.cbp & 15, cbpc = m.cbp >> 4;
+    const bool t8 = (m.flags & H264R_MBF_T8x8) != 0, i16 = m.mb_type == H264R_I_16x16;
+    const int16_t* cac = lv + 64 * __popc(cbpl);                     // include/h264r.h level layout
+    const int16_t* ldc = cac + (cbpc == 2 ? 128 : 0);
+    const int16_t* cdc = ldc + (i16 ? 16 : 0);
+    {
+        const int b8 = t >> 6, k = t & 63;
+        if ((cbpl >> b8) & 1) {
+            const int lev = lv[__popc(cbpl & ((1 << b8) - 1)) * 64 + k];
+            if (!t8) {
+                const int b4 = k >> 4, pos = k & 15;
+                const int bx = (b8 & 1) * 2 + (b4 & 1), by = (b8 >> 1) * 2 + (b4 >> 1);
+                if (!(i16 && pos == 0)) R.cof[0][(by * 4 + pos / 4) * 16 + bx * 4 + pos % 4] = lev;
+            } else
+                R.cof[0][((b8 >> 1) * 8 + k / 8) * 16 + (b8 & 1) * 8 + k % 8] = lev;
+        }
+    }
+    if (t < 128 && cbpc == 2) {                                        // chroma AC
+        const int pl = 1 + (t >> 6), k = t & 63, b = k >> 4, pos = k & 15;
+        if (pos) R.cof[pl][((b / 2) * 4 + pos / 4) * 8 + (b % 2) * 4 + pos % 4] = cac[(pl - 1) * 64 + b * 16 + pos];
+    }
+    if (t >= 192 && t < 208 && i16) R.cof[0][((t - 192) >> 2) * 4 * 16 + ((t - 192) & 3) * 4] = ldc[t - 192];
+    if (t >= 208 && t < 216 && cbpc) {                                 // chroma DC
+        const int pl = 1 + ((t - 208) >> 2), k = (t - 208) & 3;
+        R.cof[pl][((k >> 1) * 4) * 8 + (k & 1) * 4] = cdc[(pl - 1) * 4 + k];
+    }
+}
+
+// My samples of the lossless residual (bypass_4x4 / _8x8 / _16x16 / _chroma, transform.cc:736-822,
+// chosen by inverse_transform_* :986-1049): the levels accumulated down the columns of their block
+// for a vertical prediction mode, along its rows for a horizontal one, plain otherwise.  A luma
+// block takes its Intra4x4 / Intra8x8PredMode -- of an inter MB too (:993,1008) -- or the MB's
+// Intra16x16PredMode; chroma intra_chroma_pred_mode (vertical 2, horizontal 1).  Blocks the cbp
+// leaves uncoded hold zeros.  vl: luma sample t; vc: chroma sample t & 63 of plane 1 + t / 64.
+DEV void mb_bypass_dpcm(const h264r_mb& m, const ResLds& R, int t, int& vl, int& vc)
+{
+    {
+        const int x = t & 15, y = t >> 4;
+        const int n = m.mb_type == H264R_I_16x16 ? 16 : m.mb_type == H264R_I_8x8 ? 8 : m.mb_type == H264R_I_4x4 ? 4
+                    : (m.flags & H264R_MBF_T8x8) ? 8 : 4;
+        const int x0 = x & ~(n - 1), y0 = y & ~(n - 1);
+        const int bk = n == 4 ? (y >> 3) * 8 + ((y >> 2) & 1) * 2 + (x >> 3) * 4 + ((x >> 2) & 1) : (y >> 3) * 2 + (x >> 3);
+        const int mode = n == 16 ? m.i16_mode : (m.ipred[bk >> 1] >> ((bk & 1) * 4)) & 15;
+        int v = R.cof[0][t];
+        if (mode == 0) for (int k = y0; k < y; ++k) v += R.cof[0][k * 16 + x];
+        else if (mode == 1) for (int k = x0; k < x; ++k) v += R.cof[0][y * 16 + k];
+        vl = v;
+    }
+    vc = 0;
+    if (t < 128) {
+        const int pl = 1 + (t >> 6), e = t & 63, x = e & 7, y = e >> 3;
+        int v = R.cof[pl][e];
+        if (m.chroma_mode == 2) for (int k = 0; k < y; ++k) v += R.cof[pl][k * 8 + x];
+        else if (m.chroma_mode == 1) for (int k = 0; k < x; ++k) v += R.cof[pl][y * 8 + k];
+        vc = v;
+    }
+}
+
+// The residual of one 4:2:0 MB: R.cof holds it on return.  Blocks the cbp leaves uncoded have zero
+// coefficients, so their residual is zero and clip(residual + prediction) is the prediction
+// (construction transform.cc:913-984).
+DEV void mb_residual(const h264r_mb& m, const int16_t* lv, const h264r_quant& q, ResLds& R, int t)
+{
+    for (int k = t; k < 3 * 256; k += 256) (&R.cof[0][0])[k] = 0;
+    __syncthreads();
+    if (m.flags & H264R_MBF_BYPASS) {
+        mb_bypass_levels(m, lv, R, t);
+        __syncthreads();
+        int vl, vc;
+        mb_bypass_dpcm(m, R, t, vl, vc);
+        __syncthreads();
+        R.cof[0][t] = vl;
+        if (t < 128) R.cof[1 + (t >> 6)][t & 63] = vc;
+        __syncthreads();
+        return;
+    }
+    mb_coefs(m, lv, q, R, t, false);
+    __syncthreads();
+    mb_itrans((m.flags & H264R_MBF_T8x8) != 0, R, t);
+}
+
+// An inter MB of an SP slice, Transform::inverse_transform_sp (transform.cc:1267-1300): itrans_sp
+// per luma 4x4 block (:1132-1187: the prediction enters in the transform domain, the
+// reconstruction is the clipped inverse transform alone), then per chroma plane itrans_sp_cr
+// (:1190-1265) and inverse_transform_chroma, which adds the prediction once more (itrans_sp_cr
+// keeps mb_pred, :1209).  pr: the MB's prediction (luma 16 x 16, chroma 8 x 8 per plane).  R.cof
+// holds the residual on return (luma: the reconstruction before its clip).
+DEV void mb_sp(const h264r_mb& m, const h264r_slice& sl, const int16_t* lv, const h264r_quant& q, ResLds& R,
+               const int (*pr)[256], int t)
+{
+    for (int k = t; k < 3 * 256; k += 256) (&R.cof[0][0])[k] = 0;
+    __syncthreads();
+    mb_coefs(m, lv, q, R, t, true);
+    __syncthreads();
+    const int sw = sl.sp_switch;
+    if (t < 24) {                                                     // forward_4x4 of the prediction
+        const int pl = t < 16 ? 0 : 1 + ((t - 16) >> 2), bk = t < 16 ? t : (t - 16) & 3, w = pl ? 8 : 16;
+        const int x0 = pl ? (bk & 1) * 4 : (bk & 3) * 4, y0 = pl ? (bk >> 1) * 4 : (bk >> 2) * 4;
+        int c[4][4];
+        for (int j = 0; j < 4; ++j) {
+            const int* p = &pr[pl][(y0 + j) * w + x0];
+            fwd4(p[0], p[1], p[2], p[3], c[j][0], c[j][1], c[j][2], c[j][3]);
+        }
+        for (int i = 0; i < 4; ++i) fwd4_inplace(c[0][i], c[1][i], c[2][i], c[3][i]);
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < 4; ++i) {
+                const int e = (y0 + j) * w + x0 + i;
+                if (!pl) R.cof[0][e] = sp_luma_coef(R.cof[0][e], c[j][i], j, i, m.qp_y, sl.qs_y, sw);
+                else R.tmp[pl][e] = c[j][i];                          // its (0, 0) feeds the chroma DC below
+            }
+    }
+    if (t >= 64 && t < 192) {                                          // chroma AC, from the prediction samples
+        const int pl = 1 + ((t - 64) >> 6), e = (t - 64) & 63;
+        R.cof[pl][e] = sp_chroma_ac(R.cof[pl][e], pr[pl][e], (e >> 3) & 3, e & 3, m.qp_c[pl - 1], sl.qs_c[pl - 1], sw);
+    }
+    __syncthreads();
+    if (t == 16 || t == 20) {                                          // chroma DC (replaces the AC pass's (0, 0))
+        const int pl = t == 16 ? 1 : 2, cbpc = m.cbp >> 4;
+        const int16_t* cdc = lv + 64 * __popc(m.cbp & 15) + (cbpc == 2 ? 128 : 0) + (pl - 1) * 4;
+        const int c00 = R.tmp[pl][0], c04 = R.tmp[pl][4], c40 = R.tmp[pl][32], c44 = R.tmp[pl][36];
+        const int cp[4] = {c00 + c40 + c04 + c44, c00 - c40 + c04 - c44, c00 + c40 - c04 - c44, c00 - c40 - c04 + c44};
+        int mp[4];
+        for (int k = 0; k < 4; ++k) mp[k] = sp_chroma_dc(cbpc ? cdc[k] : 0, cp[k], m.qp_c[pl - 1], sl.qs_c[pl - 1], sw);
+        R.cof[pl][0] = (mp[0] + mp[1] + mp[2] + mp[3]) >> 1;
+        R.cof[pl][4] = (mp[0] + mp[1] - mp[2] - mp[3]) >> 1;
+        R.cof[pl][32] = (mp[0] - mp[1] + mp[2] - mp[3]) >> 1;
+        R.cof[pl][36] = (mp[0] - mp[1] - mp[2] + mp[3]) >> 1;
+    }
+    __syncthreads();
+    mb_itrans(false, R, t);
 }
 
 // ------------------------------------------------------------------ motion compensation
@@ -808,9 +958,22 @@ using namespace h264r;
 extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, int* err)
 {
     __shared__ ResLds R;
+    __shared__ int pr[3][256];                                             // an SP MB's prediction
     const int nmb = b.width_mbs * b.height_mbs, pic = blockIdx.x / nmb, r = blockIdx.x % nmb, t = threadIdx.x;
     const MPic P = mpic(b, pic);
     const h264r_mb m = P.mbs[r];
+    const h264r_slice& sl = P.sl[m.slice];
+    const bool sp = sl.slice_type == H264R_SLICE_SP;
+    // What this launch sequence does not decode (include/h264r.h H264R_MBAFF_FRAME) is reported in the
+    // context's error word, for h264r_check / h264r_picture_wait; the MB is left undecoded.
+    const int other = (r / P.wmb) & 1 ? r - P.wmb : r + P.wmb;             // the pair's other MB
+    if (b.pics[pic].structure != H264R_MBAFF_FRAME || sl.wp_mode == 2 || m.mb_type == H264R_SI ||
+        sl.slice_type == H264R_SLICE_SI || ((m.flags ^ P.mbs[other].flags) & H264R_MBF_FIELD) ||
+        (sp && ((m.flags & H264R_MBF_T8x8) || sl.qs_y > 51 || sl.qs_c[0] < 0 || sl.qs_c[0] >= 6 || sl.qs_c[1] < 0 ||
+                sl.qs_c[1] >= 6))) {
+        if (t == 0) atomicOr(err, 8);
+        return;
+    }
     const bool pcm = m.mb_type == H264R_I_PCM;
     if ((m.flags & H264R_MBF_INTRA) && !pcm) return;
     const int Wl = P.wmb * 16, Wc = P.wmb * 8;
@@ -827,18 +990,29 @@ extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, i
         }
         return;
     }
+    const int x = t & 15, y = t >> 4, cpl = 1 + ((t >> 6) & 1), ck = t & 63, cx = ck & 7, cy = ck >> 3;
+    if (sp) {                                                              // decoder.cc:256-257
+        pr[0][t] = inter_sample(P, r, 0, x, y, err);
+        if (t < 128) pr[cpl][ck] = inter_sample(P, r, cpl, cx, cy, err);
+        mb_sp(m, sl, lv, *P.q, R, pr, t);                                  // its first barrier orders pr
+        mloc(P, r, 16, 16, x, y, gx, gy);
+        P.out[0][(size_t)gy * Wl + gx] = (uint8_t)clip255(R.cof[0][t]);
+        if (t < 128) {
+            mloc(P, r, 8, 8, cx, cy, gx, gy);
+            P.out[cpl][(size_t)gy * Wc + gx] = (uint8_t)clip255(R.cof[cpl][ck] + pr[cpl][ck]);
+        }
+        return;
+    }
     mb_residual(m, lv, *P.q, R, t);
     {
-        const int x = t & 15, y = t >> 4;
         const int v = clip255(R.cof[0][t] + inter_sample(P, r, 0, x, y, err));
         mloc(P, r, 16, 16, x, y, gx, gy);
         P.out[0][(size_t)gy * Wl + gx] = (uint8_t)v;
     }
     if (t < 128) {
-        const int pl = 1 + (t >> 6), k = t & 63, x = k & 7, y = k >> 3;
-        const int v = clip255(R.cof[pl][k] + inter_sample(P, r, pl, x, y, err));
-        mloc(P, r, 8, 8, x, y, gx, gy);
-        P.out[pl][(size_t)gy * Wc + gx] = (uint8_t)v;
+        const int v = clip255(R.cof[cpl][ck] + inter_sample(P, r, cpl, cx, cy, err));
+        mloc(P, r, 8, 8, cx, cy, gx, gy);
+        P.out[cpl][(size_t)gy * Wc + gx] = (uint8_t)v;
     }
 }
 

@@ -7,49 +7,9 @@
 //   as it stands (see oracle/h264r_oracle.c sp_mb for its quirks).
 #pragma once
 #include "mb_inter4.h"
+#include "sp_math.h"
 
 namespace h264r {
-
-__device__ static const uint8_t SP_A[16] = {16, 20, 16, 20, 20, 25, 20, 25, 16, 20, 16, 20, 20, 25, 20, 25};
-DEV int sp_sgn(int x) { return (x >= 0) - (x < 0); }                                   // defines.h:73-77
-DEV int sp_ls2(int m, int j, int i)                                                     // LevelScale2 :1105-1130
-{
-    const int cls = (j & 1) + (i & 1);
-    constexpr int v0[6] = {13107, 11916, 10082, 9362, 8192, 7282};
-    constexpr int v1[6] = {8066, 7490, 6554, 5825, 5243, 4559};
-    constexpr int v2[6] = {5243, 4660, 4194, 3647, 3355, 2893};
-    return cls == 0 ? v0[m] : (cls == 1 ? v1[m] : v2[m]);
-}
-DEV int sp_dq(int m, int j, int i)                                                      // dequant_coef :93-100
-{
-    constexpr int v0[6] = {10, 11, 13, 14, 16, 18};
-    constexpr int v1[6] = {13, 14, 16, 18, 20, 23};
-    constexpr int v2[6] = {16, 18, 20, 23, 25, 29};
-    const int cls = (j & 1) + (i & 1);
-    return cls == 0 ? v0[m] : (cls == 1 ? v1[m] : v2[m]);
-}
-// One coefficient of itrans_sp (luma, :1158-1178): cr the dequantised level, cp the
-// transformed prediction; returns the re-dequantised coefficient.
-DEV int sp_luma_coef(int cr, int cp, int j, int i, int qp, int qs, int sw)
-{
-    const int ls = sp_ls2(qs % 6, j, i);
-    int cij;
-    if (sw) {
-        cij = cr + sp_sgn(cp) * ((iabs(cp) * ls + (1 << (14 + qs / 6))) >> (15 + qs / 6));
-    } else {
-        const int cs = cp + ((int)((unsigned)(cr * sp_dq(qp % 6, j, i) * SP_A[j * 4 + i]) << (qp / 6)) >> 10);
-        cij = sp_sgn(cs) * ((iabs(cs) * ls + (1 << (14 + qs / 6))) >> (15 + qs / 6));
-    }
-    const int dq = sp_dq(qs % 6, j, i);
-    return qs >= 24 ? (int)((unsigned)(cij * dq) << (qs / 6 - 4)) : (cij * dq + (1 << (3 - qs / 6))) >> (4 - qs / 6);
-}
-// 4-point forward core transform (forward_4x4 rows / columns, :560-594)
-DEV void fwd4(int p0, int p1, int p2, int p3, int& c0, int& c1, int& c2, int& c3)
-{
-    const int e0 = p0 + p3, e1 = p1 + p2, e2 = p1 - p2, e3 = p0 - p3;
-    c0 = e0 + e1; c1 = e2 + (e3 << 1); c2 = e0 - e1; c3 = e3 - (e2 << 1);
-}
-DEV void fwd4_inplace(int& a, int& b, int& c, int& d) { fwd4(a, b, c, d, a, b, c, d); }
 
 // itrans_sp of my 4x4 luma block (:1132-1187), all in-lane, and its store
 DEV void inter4_sp_luma(uint8_t* rmb, const h264r_mb& q, const h264r_slice* __restrict__ qs, const Inter4Lane& L, const Inter4Res& R,

@@ -289,8 +289,7 @@ int h264r_synth_picture(const h264r_synth_cfg* c, int index, h264r_mb* mbs, int1
         c->num_slices > c->height_mbs || c->num_refs < 0 || c->num_refs > H264R_MAX_REFS ||
         c->structure < H264R_FRAME || c->structure > H264R_MBAFF_FRAME ||
         (c->structure == H264R_MBAFF_FRAME && ((c->height_mbs & 1) || c->num_slices > c->height_mbs / 2 ||
-                                               (c->chroma_format != 0 && c->chroma_format != 1) || c->wp_mode == 2 ||
-                                               c->sp_slices || c->lossless_permille)) ||
+                                               (c->chroma_format != 0 && c->chroma_format != 1) || c->wp_mode == 2)) ||
         (c->kind != H264R_SYNTH_INTRA && c->num_refs < 1) || c->qp_min < 0 || c->qp_max > 51 ||
         c->qp_min > c->qp_max || (c->chroma_format >= 2 && c->structure != H264R_FRAME) ||
         c->chroma_format < 0 || c->chroma_format > 4)

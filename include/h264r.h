@@ -231,7 +231,15 @@ typedef struct h264r_quant {
  * 123-173: the geometric sample of the frame, the MB holding it), and the loop filter follows
  * Deblock::strength / filter_edge (deblock.cc:78-289, 418-535): mixed frame / field edges, the
  * top edge of a frame MB under a field pair filtered as two field edges, mvlimit 2 in field MBs.
- * 4:2:0 only; not with SP slices, lossless MBs or implicit weights (H264R_EUNSUPPORTED). */
+ * SP slices (QsC < 6, no 8x8 transform; a field MB's prediction is its field prediction; an SP MB counts
+ * as intra for bS) and lossless MBs (H264R_MBF_BYPASS, as in frames) are decoded.  These two are pinned by
+ * tests/golden/mbaff_ext.json against the reference decoder itself; the CPU oracle does not restate them.
+ * 4:2:0 only.  Not decoded: implicit weights (wp_mode 2: a field MB needs per-parity POC weights, which
+ * h264r_slice has no room for) and SI MBs.  The streaming API returns H264R_EUNSUPPORTED for wp_mode 2 and
+ * H264R_EINVAL for a pair whose MBs disagree on H264R_MBF_FIELD; the kernels flag both on the device as
+ * well, with SI MBs and slices, an SP slice's 8x8-transform MBs or QsC >= 6, and a picture of a batch with
+ * mbaff set whose structure is not H264R_MBAFF_FRAME: the launch's output is then invalid and h264r_check
+ * (h264r_picture_wait for the streaming API) returns H264R_EDEVICE. */
 #define H264R_MBAFF_FRAME   3
 typedef struct h264r_pic {
     int32_t  constrained_intra_pred;  /* pps.constrained_intra_pred_flag */
@@ -271,7 +279,9 @@ typedef struct h264r_batch {
     uint8_t*            out_v;
     int64_t             ref_planes_stride;   /* pointers; 0 = one table for the batch (above) */
     int32_t             mbaff;       /* ABI 4: nonzero = every picture is an H264R_MBAFF_FRAME (its own
-                                        launch sequence, whole pictures only); 0 = frames / fields */
+                                        launch sequence, whole pictures only; what that sequence does not
+                                        decode -- H264R_MBAFF_FRAME above -- is reported by h264r_check as
+                                        H264R_EDEVICE, never decoded silently); 0 = frames / fields */
     int32_t             colour_plane;/* ABI 4, separate_colour_plane_flag (JV) on a 4:4:4 context: 0 = off;
                                         k + 1 = every picture is colour plane k (colour_plane_id) of its
                                         frame: 4:0:0 records and levels (a PCM MB's block followed by 128

@@ -63,8 +63,10 @@ typedef struct h264r_synth_cfg {
                                     8.2.4.2.4/8.2.4.2.5 would (alternating parity); or H264R_MBAFF_FRAME:
                                     a frame of MB pairs (height_mbs even), each pair frame or field
                                     (H264R_MBF_FIELD) at random, slices of whole pair rows, a field MB's
-                                    refIdx over the 2 num_refs fields (4:2:0; wp_mode 0/1; no SP,
-                                    no lossless) */
+                                    refIdx over the 2 num_refs fields (4:2:0; wp_mode 0/1; with
+                                    sp_slices and lossless_permille as for frames -- the CPU oracle
+                                    refuses those two in MBAFF frames, tests/golden/mbaff_ext.json pins
+                                    them to the reference itself) */
     int32_t  chroma_format;      /* chroma_format_idc: 3 = 4:4:4 (every plane coded like luma: three
                                     luma-like level blocks per MB, CodedBlockPatternChroma 0, a PCM MB
                                     3 x 256 samples; frame pictures); 2 = 4:2:2 (chroma 8 x 16 per MB:
