@@ -36,6 +36,18 @@
  * (picture.cc:34, decoder.cc:199, deblock.cc:498,522); the output holds the luma plane alone.
  * Output: Y plane then Cb then Cr, 8-bit, unpadded.
  *
+ * H264R_INPUTS=<file> (tests/_oracle.py run_reference(inputs=...), the directed extreme-value cases
+ * of tests/extremes.py): after h264r_synth_picture the picture's arrays, and for every DPB slot the
+ * generated planes, are replaced by the file's; the cfg on argv still supplies the SPS / PPS level
+ * fields (size, kind, weighting, 8x8 transform, lossless, structure, chroma format, the slot count
+ * and POCs).  Little-endian, no padding between the parts:
+ *   int32  magic 0x58343632, version 1, number of DPB slots (== h264r_synth_ref_frames), 0
+ *   int64  n_levels
+ *   h264r_mb[W*H], int16 levels[n_levels], uint32 mv[2][4H][4W], int8 ref_idx[2][4H][4W],
+ *   h264r_slice[num_slices], h264r_pic
+ *   per slot: Y [16 FH][16 W], then Cb and Cr [FH * MbHeightC][W * MbWidthC] (none for 4:0:0)
+ * (FH: the frame's MB rows, 2H for a field picture).
+ *
  * Timing mode (H264R_TIME_REPS=<n>): the reconstruction of the picture -- the
  * coefficient push (inverse scan + dequantisation), Decoder::decode of every MB and
  * deblock_filter -- runs n times back to back on one thread (every pass rewrites every
@@ -130,6 +142,26 @@ int main(int argc, char** argv)
         fprintf(stderr, "synth failed\n");
         return 3;
     }
+    /* H264R_INPUTS=<file>: the picture's arrays and the DPB planes from a file instead of the
+       generator (tests/extremes.py: directed extreme-value inputs); layout in the header comment */
+    FILE* xin = nullptr;
+    int32_t xin_slots = 0;
+    if (const char* xp = getenv("H264R_INPUTS")) {
+        xin = fopen(xp, "rb");
+        int32_t hd[4];
+        int64_t nl = 0;
+        auto rd = [&](void* p, size_t n) { return n == 0 || fread(p, n, 1, xin) == 1; };
+        if (!xin || !rd(hd, sizeof(hd)) || hd[0] != 0x58343632 || hd[1] != 1 || !rd(&nl, sizeof(nl)) ||
+            nl < 0 || (size_t)nl > levels.size() || hd[3] != 0 ||
+            !rd(mbs.data(), sizeof(h264r_mb) * NMB) || !rd(levels.data(), sizeof(int16_t) * (size_t)nl) ||
+            !rd(mv.data(), sizeof(uint32_t) * mv.size()) || !rd(ref_idx.data(), ref_idx.size()) ||
+            !rd(slices.data(), sizeof(h264r_slice) * slices.size()) || !rd(&pic, sizeof(pic))) {
+            fprintf(stderr, "cannot read %s\n", xp);
+            return 2;
+        }
+        nlev = nl;
+        xin_slots = hd[2];
+    }
 
     VideoParameters* vid = new VideoParameters();
     sps_t* sps = new sps_t();
@@ -178,6 +210,14 @@ int main(int argc, char** argv)
     std::vector<uint8_t> ty(W * 16 * FH * 16), tu(W * RW * FH * RH + 1), tv(W * RW * FH * RH + 1);
     for (int s = 0; s < nfr; ++s) {
         h264r_synth_refpic_fmt(cfg.seed, s, W, FH, jv ? 3 : cfg.chroma_format, ty.data(), tu.data(), tv.data());
+        if (xin) {                                       /* H264R_INPUTS: this slot's planes */
+            const size_t nc = (size_t)W * RW * FH * RH;
+            if (xin_slots != nfr || fread(ty.data(), ty.size(), 1, xin) != 1 ||
+                (nc && (fread(tu.data(), nc, 1, xin) != 1 || fread(tv.data(), nc, 1, xin) != 1))) {
+                fprintf(stderr, "H264R_INPUTS: %d slots wanted, planes of slot %d unreadable\n", nfr, s);
+                return 2;
+            }
+        }
         for (int f = 0; f < (fld ? 2 : 1); ++f) {
             storable_picture* r = new storable_picture(vid, fld ? (f ? BOTTOM_FIELD : TOP_FIELD) : FRAME,
                                                        W * 16, FH * 16, W * RW, FH * RH, 1);
@@ -213,6 +253,14 @@ int main(int argc, char** argv)
                 r->frame = fr;
                 (f ? fr->bottom_field : fr->top_field) = r;
             }
+        }
+    }
+    if (xin) {                                           /* the file ends with the last slot's planes */
+        const bool more = fgetc(xin) != EOF;
+        fclose(xin);
+        if (more || xin_slots != nfr) {
+            fprintf(stderr, "H264R_INPUTS: %d slots wanted, %d named%s\n", nfr, xin_slots, more ? ", bytes left over" : "");
+            return 2;
         }
     }
     /* RefPicList entry -> storable_picture (include/h264r.h: slot | H264R_REF_BOTTOM for fields) */

@@ -151,12 +151,14 @@ def decode_jv_plane(p: synth.Picture, k: int, qm=None):
 
 
 def run_reference(cfg: A.SynthCfg, index: int, recon_only: bool = False, time_reps: int = 0, qm=None,
-                  jv_plane: int | None = None):
+                  jv_plane: int | None = None, inputs=None):
     """Planes produced by the compiled reference decoder (this container only).  With
     time_reps > 0 the driver reconstructs the picture that many times on one thread and
     (planes, macroblocks, seconds) is returned (ref_driver.cc timing mode).  qm = (m4, m8):
     explicit SPS scaling lists (all present).  jv_plane = k: the (4:0:0) picture decoded as colour plane
-    k of a separate-colour-plane frame; the single decoded plane is returned."""
+    k of a separate-colour-plane frame; the single decoded plane is returned.  inputs = (picture,
+    refs): the driver decodes these arrays and DPB planes instead of the generated ones
+    (H264R_INPUTS, layout in ref_driver.cc's header; tests/extremes.py)."""
     drv = build_ref()
     W, H = cfg.width_mbs, cfg.height_mbs
     with tempfile.TemporaryDirectory() as td:
@@ -176,6 +178,18 @@ def run_reference(cfg: A.SynthCfg, index: int, recon_only: bool = False, time_re
             np.concatenate([np.ascontiguousarray(qm[0], np.int32).ravel(),
                             np.ascontiguousarray(qm[1], np.int32).ravel()]).tofile(qf)
             env["H264R_QMATRIX"] = qf
+        if inputs is not None:
+            p, refs = inputs
+            xf = os.path.join(td, "inputs.bin")
+            with open(xf, "wb") as f:
+                f.write(np.array([0x58343632, 1, len(refs), 0], np.int32).tobytes())
+                f.write(np.array([len(p.levels)], np.int64).tobytes())
+                for a in (p.mbs, p.levels, p.mv, p.ref_idx, p.slices, p.pic):
+                    f.write(np.ascontiguousarray(a).tobytes())
+                for planes in refs:
+                    for a in planes:
+                        f.write(np.ascontiguousarray(a).tobytes())
+            env["H264R_INPUTS"] = xf
         r = subprocess.run([str(a) for a in args], capture_output=True, text=True, env=env)
         if r.returncode != 0:
             raise RuntimeError(f"ref_driver failed ({r.returncode}): {r.stderr[-2000:]}")

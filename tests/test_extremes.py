@@ -1,0 +1,411 @@
+"""Directed extreme-value inputs (tests/extremes.py): the host-side census and the reference pin.
+
+CPU only.  A directed input that misses its target proves nothing, so for every family the census
+asserts, from the inputs and the oracle alone, that the target is hit: blocks exactly at the packed
+transforms' bound in packed waves and one past it in fallback waves, the 6-tap intermediates at their
+extremes, every border crossed by every amount, every listed weight used, every designed deblocking
+line filtered exactly as 8.7.2 says.  These are conditions, not measurements.
+
+The GPU is compared with the oracle (tests/test_gpu_extremes.py); here the oracle is pinned to the
+unmodified reference decoder on the same inputs: tests/golden/extremes.json holds the MD5s of what
+the compiled reference made of each picture (tests/golden/make_extremes.py).
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import _oracle as O
+import extremes as X
+from h264r import _abi as A
+from h264r import synth
+
+_HERE = os.path.dirname(__file__)
+EXT = json.load(open(os.path.join(_HERE, "golden", "extremes.json")))["cases"]
+_IDS = [c["name"] for c in EXT]
+
+
+@pytest.fixture(scope="module")
+def quant():
+    return O.quant_flat()[0]
+
+
+# ---------------------------------------------------------------- the reference pin
+def test_fixture_cases():
+    """The committed file holds the builders' cases, every picture of each, MD5s only."""
+    assert _IDS == list(X.CASES)
+    for c in EXT:
+        assert set(c) == {"name", "refs_md5", "pictures"}
+        assert 1 <= len(c["pictures"]) <= 8
+        for p in c["pictures"]:
+            assert set(p) == {"cfg", "index", "input_md5", "recon_md5", "out_md5"}
+
+
+@pytest.mark.parametrize("fx", EXT, ids=_IDS)
+def test_built_inputs_match_fixture(fx):
+    """Builder drift: the inputs built here are the ones the reference decoded."""
+    c = X.build(fx["name"])
+    assert [p.cfg.as_dict() for p in c.pics] == [p["cfg"] for p in fx["pictures"]]
+    assert [p.index for p in c.pics] == [p["index"] for p in fx["pictures"]]
+    assert X.digests(c) == dict(inputs=[p["input_md5"] for p in fx["pictures"]], refs=fx["refs_md5"])
+    again = X.CASES[fx["name"]](O.lib())              # seeded: a second build is byte-identical
+    assert [synth.input_digest(p) for p in again.pics] == X.digests(c)["inputs"] and X.refs_digest(again.refs) == fx["refs_md5"]
+
+
+@pytest.mark.parametrize("fx", EXT, ids=_IDS)
+def test_oracle_matches_reference_md5s(fx):
+    """The CPU oracle's reconstruction and output of every picture equal the reference's."""
+    c = X.build(fx["name"])
+    for i, (p, want) in enumerate(zip(c.pics, fx["pictures"])):
+        for stage, key in (("recon", "recon_md5"), ("full", "out_md5")):
+            got = O.decode(p, c.refs, stage=stage)
+            assert {k: X.md5(got[j]) for j, k in enumerate("YUV")} == want[key], f"picture {i} {stage}"
+
+
+@pytest.mark.reference
+@pytest.mark.skipif(not O.reference_available(), reason="needs the reference sources")
+@pytest.mark.parametrize("fx", EXT, ids=_IDS)
+def test_live_reference_reproduces_fixture(fx):
+    """Every case straight from the compiled reference (milliseconds per picture)."""
+    c = X.build(fx["name"])
+    for i, (p, want) in enumerate(zip(c.pics, fx["pictures"])):
+        rec = O.run_reference(p.cfg, p.index, recon_only=True, inputs=(p, c.refs))
+        assert {k: X.md5(rec[j]) for j, k in enumerate("YUV")} == want["recon_md5"], f"picture {i}"
+        out = O.run_reference(p.cfg, p.index, inputs=(p, c.refs))
+        assert {k: X.md5(out[j]) for j, k in enumerate("YUV")} == want["out_md5"], f"picture {i}"
+
+
+# ---------------------------------------------------------------- census: R
+@pytest.mark.parametrize("name", ["r1_at_bound", "r3_flat_at_bound"])
+def test_census_r_at_bound(quant, name):
+    """Every coded wave is packed and its largest block is exactly at 32700; the plain-integer
+    inverse of such blocks reaches an intermediate of 32700 + 32 and stays inside int16, and the
+    residual reaches both (+-32700 + 32) >> 6."""
+    c = X.build(name)
+    at, big_max, res, lone = 0, 0, set(), set()
+    for p in c.pics:
+        waves = X.wave_sums(p, quant)
+        for (lc, ls, t8, _, _), (lp, _) in zip(waves, X.wave_paths(p, quant)):
+            if lc and ls:
+                assert not t8 and lp == "packed" and max(ls) == X.PK_RES_MAX, (lp, max(ls))
+                at += sum(s == X.PK_RES_MAX for s in ls)
+        for _, d in X.luma_blocks(p, quant):
+            if sum(abs(v) for r in d for v in r) == X.PK_RES_MAX:
+                big, r = X.idct4x4_trace(d)
+                assert big <= 32732
+                big_max = max(big_max, big)
+                res |= {v for row in r for v in row}
+                corners = {(i, j): r[i][j] for i in (0, 3) for j in (0, 3)}
+                for g, ext in ((1, (X.PK_RES_MAX + 32) >> 6), (-1, (-X.PK_RES_MAX + 32) >> 6)):
+                    hit = [k for k, v in corners.items() if v == ext]
+                    if len(hit) == 1 and all(abs(v) < abs(ext) - 50 for k, v in corners.items() if k != hit[0]):
+                        lone.add((hit[0], g))
+    # +- sum |d| on one corner sample alone, for each of the four corners (mass on the odd positions)
+    assert lone == {((i, j), g) for i in (0, 3) for j in (0, 3) for g in (1, -1)}, lone
+    assert at > 100 and big_max == X.PK_RES_MAX + 32
+    assert (X.PK_RES_MAX + 32) >> 6 in res and (-X.PK_RES_MAX + 32) >> 6 in res
+    if name.startswith("r3"):
+        assert {int(pl[0, 0]) for planes in c.refs for pl in planes} == {0, 255}
+        assert {s for p in c.pics for _, _, _, s, _, _ in X.predicted_blocks(p)} >= {0, 1}
+
+
+@pytest.mark.parametrize("name", ["r2_over", "r3_flat_over"])
+def test_census_r_over(quant, name):
+    """Every designed wave falls back because of its one designed block: 32701 exactly where the
+    scales reach it, sums whose + 32 passes int16, single coefficients on both sides of int16 and at
+    40000, residuals past int16 after the shift."""
+    c = X.build(name)
+    paths = [X.wave_paths(p, quant) for p in c.pics]
+    sums = [X.wave_sums(p, quant) for p in c.pics]
+    kinds = set()
+    for pi, w, kind in c.info["design"]:
+        assert paths[pi][w][0] == "fallback", (pi, w, kind)
+        ls = sorted(sums[pi][w][1])
+        if kind.startswith("sum"):
+            assert ls[-1] == int(kind[3:-1]) and ls[-2] <= X.PK_RES_MAX, (kind, ls[-2:])
+        kinds.add(kind)
+    assert {"sum32701+", "sum32701-", "one<=32767", "one>=32768", "one<=-32768", "one40000", "near2^24"} <= kinds
+    assert any(k.startswith("sum3273") or k.startswith("sum3274") for k in kinds)     # + 32 passes 32767
+    single = [v for p in c.pics for _, d in X.luma_blocks(p, quant) for v in [[x for r in d for x in r if x]] if len(v) == 1]
+    vals = {v[0] for v in single}
+    assert any(32767 - 32 < v <= 32767 for v in vals) and any(32768 <= v < 32768 + 64 for v in vals)
+    assert any(-32768 - 64 < v <= -32768 for v in vals) and any(40000 - 64 < v <= 40000 for v in vals)
+    assert any((v + 32) >> 6 > 32767 for v in vals) and any((v + 32) >> 6 < -32768 for v in vals)
+    assert max(abs(v) for v in vals) <= 1 << 24
+
+
+def test_census_r_chroma(quant):
+    """The chroma measure: at the bound every coded wave is packed with its largest measure exactly
+    32700, reached by cbpc 1 (DC through the Hadamard) and cbpc 2, with the mass in Cb and in Cr;
+    over the bound every designed wave falls back, at 32701 exactly where the scales reach it."""
+    c = X.build("r4_chroma_at_bound")
+    seen = set()
+    for p in c.pics:
+        n_at = 0
+        for (_, _, _, cc, cs), (_, cp) in zip(X.wave_sums(p, quant), X.wave_paths(p, quant)):
+            if cc:
+                assert cp == "packed" and max(cs) <= X.PK_RES_MAX
+                n_at += sum(s == X.PK_RES_MAX for s in cs)
+        assert n_at > 0
+        for mi, m in enumerate(p.mbs):
+            if int(m["flags"]) & A.MBF_INTRA or not int(m["cbp"]) >> 4:
+                continue
+            cs = X.wave_sums(X.one_mb(p, mi), quant)[0][4]
+            if max(cs) == X.PK_RES_MAX:
+                _, cac, _, cdc, _ = X.layout(m)
+                o = int(m["coef_off"])
+                mass = [int(np.abs(p.levels[o + cdc + 4 * pl:o + cdc + 4 * pl + 4].astype(np.int64)).sum()) for pl in range(2)]
+                seen.add((int(m["cbp"]) >> 4, "Cb" if mass[0] > mass[1] else "Cr"))
+    assert seen == {(1, "Cb"), (1, "Cr"), (2, "Cb"), (2, "Cr")}, seen
+    c = X.build("r4_chroma_over")
+    paths = [X.wave_paths(p, quant) for p in c.pics]
+    sums = [X.wave_sums(p, quant) for p in c.pics]
+    tops = set()
+    for pi, w, cbpc in c.info["design"]:
+        assert paths[pi][w][1] == "fallback"
+        tops.add((cbpc, max(sums[pi][w][4])))
+    assert (2, X.PK_RES_MAX + 1) in tops and {k for k, _ in tops} == {1, 2}, tops
+    assert all(v <= X.PK_RES_MAX + 16 for _, v in tops), tops
+
+
+@pytest.mark.parametrize("name", ["r5_amplified_intra", "r5_amplified_b", "x_mbaff_p", "x_422_p"])
+def test_census_r_amplified(quant, name):
+    """amplify(): the gain is the bound's (one more breaks it), the residual saturates samples at 0
+    and 255 in every plane, and the MB kinds the case is there for are coded."""
+    c = X.build(name)
+    assert all(k >= 100 for k in c.info["gains"]), c.info
+    for p, k in zip(c.pics, c.info["gains"]):             # one more breaks a bound (or the cap of int16 levels)
+        if k < 4000:
+            fresh = synth.picture(O.lib(), p.cfg, p.index)
+            X.amplify(fresh, k + 1)
+            with pytest.raises(AssertionError):
+                X.check_bounds(fresh)
+    types = set()
+    for p in c.pics:
+        rec = O.decode(p, c.refs, stage="recon")
+        assert all((pl == 0).any() and (pl == 255).any() for pl in rec)
+        for m in p.mbs:
+            if int(m["cbp"]) or int(m["mb_type"]) == A.I_16x16:
+                types.add((int(m["mb_type"]) if int(m["flags"]) & A.MBF_INTRA else "inter", bool(int(m["flags"]) & A.MBF_T8x8),
+                           int(m["cbp"]) >> 4))
+    if name == "r5_amplified_intra":
+        assert {t[0] for t in types} >= {A.I_4x4, A.I_8x8, A.I_16x16} and {t[2] for t in types} == {0, 1, 2}
+    else:
+        assert ("inter", False, 1) in types and ("inter", False, 2) in types
+    if name == "r5_amplified_b":
+        assert any(t[0] == "inter" and t[1] for t in types)          # 8x8 blocks feeding the packed construction
+    if name == "x_mbaff_p":
+        assert any(int(m["flags"]) & A.MBF_FIELD for p in c.pics for m in p.mbs)
+
+
+# ---------------------------------------------------------------- census: M
+def test_census_m_patterns():
+    """Over the blocks actually predicted: b1 and h1 reach 10710 and -2550, j1 42 * 10710 and
+    -10 * 10710 (the outer products) and the extremes over all 0 / 255 windows, rounded values are
+    clipped at both ends, j meets rounding ties ((j1 + 512) a multiple of 1024 with a result the clip
+    keeps), and every pattern is read under all 16 phases."""
+    cs = {n: X.mc_census(X.build(n)) for n in ("m1_stripes", "m1_outer_random", "m1_flat_checker_b")}
+    for n, r in cs.items():
+        assert all(len(v) == 16 for v in r["phases"].values()) and len(r["phases"]) >= 4, (n, r["phases"])
+    s, o = cs["m1_stripes"], cs["m1_outer_random"]
+    assert s["b"] == [-2550, 10710] and s["h"] == [-2550, 10710]
+    assert s["bclip"] == {0, 255} and o["jclip"] == {0, 255}
+    assert o["j"] == [-2 * 42 * 10 * 255, (42 * 42 + 10 * 10) * 255], o["j"]
+    for name, lo, hi in (("outer_max", None, 42 * 10710), ("outer_min", -10 * 10710, None)):
+        c = X.build("m1_outer_random")
+        slot = ("outer_max", "outer_min", "xnor", "xor", "random").index(name)
+        only = X.Case(name, c.pics, [c.refs[slot] if k == slot else tuple(np.full_like(a, 128) for a in c.refs[k])
+                                     for k in range(len(c.refs))])
+        j = X.mc_census(only)["j"]
+        assert (hi is None or j[1] == hi) and (lo is None or j[0] == lo), (name, j)
+    assert o["ties"] > 0 and cs["m1_flat_checker_b"]["ties"] > 0
+    b = X.build("m1_flat_checker_b")
+    assert any(r0 >= 0 and r1 >= 0 for p in b.pics for r0, r1 in zip(p.ref_idx[0].ravel(), p.ref_idx[1].ravel()))
+
+
+@pytest.mark.parametrize("name", ["m2_borders_p", "m2_borders_b"])
+def test_census_m_borders(name):
+    """Every border is straddled by the 9x9 luma window by each of 0..8 samples and under each of the
+    16 phases (the P case: every corner too, by each amount under each phase), the 3x3 chroma window
+    by 0..2, the level-limit vectors are there, and every DPB slot (the generator's plane and two 0 / 255
+    patterns) is read."""
+    c = X.build(name)
+    r = X.mc_census(c)
+    assert r["straddle"] == {(b, k) for b in "LRTB" for k in range(9)}
+    assert r["straddle_phase"] == {(b, ph) for b in "LRTB" for ph in range(16)}
+    assert r["chroma"] == {(b, k) for b in "LRTB" for k in range(3)}
+    assert r["mvs"] >= set(X.LIMIT_MVS)
+    assert set(r["phases"]) == {0, 1, 2} and all(len(v) == 16 for v in r["phases"].values())
+    if name == "m2_borders_p":
+        assert c.info["combos"] == 8 * 9 * 16
+        assert r["corner"] >= {(cn, k, ph) for cn in ("TL", "TR", "BL", "BR") for k in range(9) for ph in range(16)}
+    else:
+        assert {cn for cn, _, _ in r["corner"]} == {"TL", "TR", "BL", "BR"}
+        assert any((p.ref_idx[0] >= 0).any() and (p.ref_idx[1] >= 0).any() for p in c.pics)
+
+
+# ---------------------------------------------------------------- census: W
+def test_census_w():
+    """Every (logWD, weight, offset) of the issue's list is used by a single-list block, for luma and
+    chroma; the bi-prediction pairs (127, 127) and (-128, -128) at logWD 0 and (127, -128), (-128, 127)
+    at logWD 7; single-list blocks inside B slices; and the value wp_apply4 clips reaches far below 0
+    and above 255 (2 * 127 * 255 is past int16 before the shift)."""
+    single, pairs, lo, hi = X.wp_census(X.build("w_explicit_p"))
+    assert not pairs
+    assert single == {(ch, d, w, o) for ch in (False, True) for d in (0, 7) for w, o in X.W_COMBOS}
+    assert lo == -128 * 255 - 128 and hi == 127 * 255 + 127
+    for name in ("w_explicit_b_flat", "w_explicit_b_random"):
+        c = X.build(name)
+        single, pairs, lo, hi = X.wp_census(c)
+        want = {(ch, 0, 127, 127) for ch in (False, True)} | {(ch, 0, -128, -128) for ch in (False, True)}
+        want |= {(ch, 7, 127, -128) for ch in (False, True)} | {(ch, 7, -128, 127) for ch in (False, True)}
+        assert want <= pairs, want - pairs
+        assert all(-128 <= w0 + w1 <= 127 for _, d, w0, w1 in pairs if d == 7)            # 7.4.3.2
+        assert single and lo < -30000 and hi > 30000
+        for p in c.pics:
+            assert {int(s["luma_log2_wd"]) for s in p.slices} == {0, 7}
+            assert all(int(s["luma_log2_wd"]) != int(s["chroma_log2_wd"]) for s in p.slices)
+
+
+# ---------------------------------------------------------------- census: D
+def _line_samples(planes, ln, horizontal):
+    n = len(ln["line"]) // 2
+    a, e = ln["at"], ln["edge"]
+    return [int(v) for v in (planes[ln["plane"]][e - n:e + n, a] if horizontal else planes[ln["plane"]][a, e - n:e + n])]
+
+
+@pytest.mark.parametrize("name", X.D_LINE_CASES)
+def test_census_d_lines(name):
+    """Every designed line: the oracle's reconstruction holds the crafted samples, and its output
+    holds 8.7.2's filter of them under the edge's designed bS, alpha, beta and tc0 -- so samples change
+    exactly where the design says the filter is on, and p1 / q1 / p2 / q2 exactly where ap / aq and the
+    strong filter say so."""
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    outs = [(O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs)) for p in c.pics]
+    changed = 0
+    for ln in c.info["lines"]:
+        rec, full = outs[ln["pic"]]
+        assert _line_samples(rec, ln, hz) == ln["line"]
+        want = X.filter_line(ln["line"], ln["alpha"], ln["beta"], ln["bS"], ln["plane"] > 0, ln["tc0"])
+        got = _line_samples(full, ln, hz)
+        assert got == want, (ln, got, want)
+        if not X.classify(ln["line"], ln["alpha"], ln["beta"], ln["bS"], ln["plane"] > 0, ln["tc0"])["on"]:
+            assert got == ln["line"]
+        changed += got != ln["line"]
+    assert changed > 100
+
+
+@pytest.mark.parametrize("horizontal", [False, True], ids=["vertical", "horizontal"])
+def test_census_d_coverage(horizontal):
+    """What the designed lines of one edge direction cover, from their samples and parameters."""
+    lines = [dict(ln, case=n) for n in X.D_LINE_CASES if X.build(n).info["horizontal"] == horizontal for ln in X.build(n).info["lines"]]
+    cl = [(ln, X.classify(ln["line"], ln["alpha"], ln["beta"], ln["bS"], ln["plane"] > 0, ln["tc0"])) for ln in lines]
+    for chroma in (False, True):
+        sel = [(ln, c) for ln, c in cl if (ln["plane"] > 0) == chroma and ln["bS"]]
+        norm = [(ln, c) for ln, c in sel if ln["bS"] < 4]
+        alphas = {ln["alpha"] for ln, _ in norm}
+        assert {4, 255} <= alphas and len(alphas) >= 8, alphas        # index 16, mid-range, 51
+        assert {ln["bS"] for ln, _ in sel} == {1, 2, 4}
+        # alpha: flat sides with a step of alpha - 1 (on), alpha, alpha + 1 (off)
+        steps = {(ln["alpha"], c["step"] - ln["alpha"]) for ln, c in norm if c["dp1"] < ln["beta"] and c["dq1"] < ln["beta"]}
+        assert {(4, -1), (4, 0), (4, 1), (255, -1), (255, 0)} <= steps
+        assert sum({(a, -1), (a, 0), (a, 1)} <= steps for a in alphas) >= 6
+        # beta: |p1 - p0| and |q1 - q0| at beta - 1 (on) and beta (off)
+        for key in ("dp1", "dq1"):
+            other = "dq1" if key == "dp1" else "dp1"
+            edge = {(c[key] - ln["beta"], c["on"]) for ln, c in norm if c["step"] < ln["alpha"] and c[other] < ln["beta"] and ln["beta"] > 1}
+            assert {(-1, True), (0, False)} <= edge, (key, edge)
+        on = [(ln, c) for ln, c in norm if c["on"]]
+        assert {c["clip"] for _, c in on} == {-1, 0, 1}               # the delta clipped at + tc and at - tc
+        assert {c["clamp"] for _, c in on} >= {0, 255}               # clamp255 acts on p0 + d / q0 - d
+        if not chroma:
+            # |p2 - p0| and |q2 - q0| at beta - 1 and beta in all four combinations: tc = tc0 + 0 / 1 / 2
+            combos = {(c["ap"] - ln["beta"], c["aq"] - ln["beta"]) for ln, c in on}
+            assert {(a, b) for a in (-1, 0) for b in (-1, 0)} <= combos, combos
+            assert {c["tc"] - ln["tc0"] for ln, c in on} == {0, 1, 2}
+            # bS 4: |p0 - q0| at (alpha >> 2) + 1, + 2, + 3, ap / aq true on one side, both, neither
+            strong = {(c["step"] - (ln["alpha"] >> 2), c["ap"] < ln["beta"], c["aq"] < ln["beta"])
+                      for ln, c in sel if ln["bS"] == 4 and c["on"] and ln["line"][0] != ln["line"][1] and ln["line"][7] != ln["line"][6]}
+            assert {(s, a, b) for s in (1, 2, 3) for a in (False, True) for b in (False, True)} <= strong, strong
+        else:
+            assert any(c["on"] for ln, c in sel if ln["bS"] == 4) and any(not c["on"] for ln, c in sel if ln["bS"] == 4)
+    # adjacent 4-line segments of one edge with different bS: 0|1, 1|2, 2|0 (either order)
+    pairs, byedge = set(), {}
+    for ln in lines:
+        if ln["plane"] == 0 and ln["bS"] < 4:
+            byedge.setdefault((ln["case"], ln["pic"], ln["edge"]), {})[ln["at"] // 4] = ln["bS"]
+    for segs in byedge.values():
+        for k in segs:
+            if k + 1 in segs and k % 4 != 3:
+                pairs.add(frozenset((segs[k], segs[k + 1])))
+    assert {frozenset((0, 1)), frozenset((1, 2)), frozenset((2, 0))} <= pairs, pairs
+
+
+@pytest.mark.parametrize("name", X.D_EVERY_CASES)
+def test_census_d_every_edge(name):
+    """Inner edges, bS 3, Intra_16x16 at high QP and the 8x8 transform: the oracle's output equals the
+    whole loop filter restated from the designed bS of every edge segment (so samples change exactly
+    where the design says a filter is on), and the lines of the designed direction, as they stand when
+    their edge is filtered, sit on the thresholds for every bS, on MB and on inner edges."""
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    logs, skipped_on = [], 0
+    for p, d in zip(c.pics, c.info["design"]):
+        rec, full = O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs)
+        planes = [a.astype(np.int64) for a in d["want"]]
+        assert all(np.array_equal(rec[k], d["want"][k]) for k in range(3))
+        X.deblock_restate(planes, 5, 3, d["qp_y"], d["qp_c"], d["bsV"], d["bsH"], d["offa"], d["offb"],
+                          log=lambda *a: logs.append(a))
+        for k in range(3):
+            assert np.array_equal(planes[k], full[k]), (name, k, np.argwhere(planes[k] != full[k])[:3])
+        # 8x8-transform MBs: the 4x4 inner edges are not filtered, though a bS 2 line there would be on
+        want, out = (d["want"][0].T, full[0].T) if hz else (d["want"][0], full[0])
+        kind = [list(r) for r in zip(*d["kind"])] if hz else d["kind"]
+        qp = d["qp_y"].T if hz else d["qp_y"]
+        for cy, row in enumerate(kind):
+            for cx, k in enumerate(row):
+                if k != "T":
+                    continue
+                ia, ib = (min(51, max(0, int(qp[cy][cx]) + o)) for o in (d["offa"], d["offb"]))
+                for e in (4, 12):
+                    for y in (3, 4, 12):
+                        sl = (16 * cy + y, slice(16 * cx + e - 4, 16 * cx + e + 4))
+                        assert list(out[sl][3:5]) == list(want[sl][3:5])       # p0, q0: no other edge reaches them
+                        skipped_on += X.classify(want[sl], X.ALPHA[ia], X.BETA[ib], 2, False, X.TC0[ia][1])["on"]
+    assert skipped_on > 0
+    mine = [(pl, inner, bS, al, be, X.classify(line, al, be, bS, pl > 0, tc0), tc0)
+            for pl, vertical, inner, mb, bS, al, be, tc0, line in logs if vertical != hz]
+    for chroma in (False, True):
+        for inner in (False, True):
+            sel = [m for m in mine if (m[0] > 0) == chroma and m[1] == inner]
+            assert {m[2] for m in sel} == ({1, 2, 3} if inner else {1, 2, 4}), (chroma, inner)
+            for bS in {m[2] for m in sel}:
+                s = [m for m in sel if m[2] == bS]
+                assert any(m[5]["on"] for m in s) and any(not m[5]["on"] for m in s)
+                if not inner and bS < 4:
+                    continue              # MB edges of bS 1 / 2: the d_bs1 / d_mix cases hold their thresholds
+                # |p0 - q0| at alpha - 1 (on) and alpha (off, alpha alone deciding)
+                th = {m[5]["step"] - m[3] for m in s if m[3] and m[5]["dp1"] < m[4] and m[5]["dq1"] < m[4]}
+                assert {-1, 0} <= th, (chroma, inner, bS, th)
+                # |p1 - p0| / |q1 - q0| at beta - 1 and beta
+                for key in ("dp1", "dq1"):
+                    assert {-1, 0} <= {m[5][key] - m[4] for m in s if m[4] > 1}, (chroma, inner, bS, key)
+                assert max(m[3] for m in s if m[5]["on"]) == 255, (chroma, inner, bS)          # indexA 51
+                if bS < 4:                # the delta clipped at - tc and at + tc (chroma bS 3: at one end at least)
+                    clips = {m[5]["clip"] for m in s if m[5]["on"]}
+                    assert clips >= ({-1, 1} if not chroma else {-1}), (chroma, inner, bS, clips)
+    luma = [m for m in mine if m[0] == 0]
+    # bS 2 with the table's large tc0 (indexA >= 45), inner and MB edges; the strong filter at high alpha
+    assert {m[1] for m in luma if m[2] == 2 and m[6] >= 8 and m[5]["on"]} == {False, True}
+    strong = {(m[5]["step"] - (m[3] >> 2), m[5]["ap"] < m[4], m[5]["aq"] < m[4]) for m in luma if m[2] == 4 and m[3] >= 200 and m[5]["on"]}
+    assert {s for s, _, _ in strong} >= {1, 2, 3} and {(a, b) for _, a, b in strong} >= {(True, True)}, strong
+    # adjacent 4-line segments of one INNER edge with different bS
+    pairs = set()
+    for d in c.info["design"]:
+        bs = d["bsH"].T if hz else d["bsV"]
+        for bx in range(bs.shape[1]):
+            if bx % 4:
+                pairs |= {frozenset((int(bs[by, bx]), int(bs[by + 1, bx]))) for by in range(bs.shape[0] - 1) if by % 4 != 3}
+    assert {frozenset((0, 2)), frozenset((1, 2))} <= pairs, pairs

@@ -16,8 +16,7 @@ import h264r
 from h264r import _abi as A
 from h264r import batch as B
 from h264r import synth
-
-PK_RES_MAX = 32700
+from extremes import PK_RES_MAX, wave_paths
 
 # config 3 (P pictures, 4x4 transform) at 5 x 3 MBs, 6 pictures: the lower QP ranges take the packed
 # path, the upper ones the fallback (single coefficients past int16), 38..46 mixes waves of both
@@ -74,71 +73,8 @@ def _batch_vs_oracle(L, dec, cidx, W, H, n, deblocks=(A.DBG_DEBLOCK_ROWS,), qm=N
 
 
 # ---------------------------------------------------------------- the guard, on the host
-def _dq4(lev, scale, per):
-    return ((int(lev) * int(scale) << per) + 8) >> 4
-
-
-def _wave_paths(p, quant):
-    """Per wave of k_inter4r (four consecutive MBs of the picture) which residual path its luma and
-    its chroma take: 'packed', 'fallback' or None (no coded residual, or a path without the test).
-    Mirrors luma_res_4x4 / inter4_chroma_residual: the lanes of intra, PCM and lossless MBs take no part in the test."""
-    s4 = quant["scale4x4"]
-    out = []
-    nmb = len(p.mbs)
-    for a0 in range(0, nmb, 4):
-        luma_sums, chroma_sums, t8_any, luma_coded, chroma_coded = [], [], False, False, False
-        for m in p.mbs[a0:a0 + 4]:
-            flags, cbp = int(m["flags"]), int(m["cbp"])
-            if flags & A.MBF_INTRA:
-                continue
-            cbpl, cbpc = cbp & 15, cbp >> 4
-            luma_coded |= cbpl != 0
-            chroma_coded |= cbpc != 0
-            if flags & A.MBF_BYPASS:
-                continue
-            t8_any |= bool(flags & A.MBF_T8x8)
-            lv = p.levels[int(m["coef_off"]):]
-            off = 0
-            qpl = int(m["qp_scaled"][0])
-            for b8 in range(4):
-                if not (cbpl >> b8) & 1:
-                    continue
-                if not flags & A.MBF_T8x8:
-                    for k in range(4):
-                        blk = lv[off + k * 16: off + k * 16 + 16]
-                        luma_sums.append(sum(abs(_dq4(blk[i], s4[1][0][qpl % 6][i], qpl // 6)) for i in range(16)))
-                off += 64
-            cac = off if cbpc == 2 else -1
-            off += 128 if cbpc == 2 else 0
-            cdc = off                      # (an inter MB has no luma DC block)
-            if cbpc:
-                for cb in range(4):
-                    quad = np.zeros((2, 4), np.int64)      # [plane][quadrant of the 4x4 block]
-                    for pl in range(2):
-                        qpc = int(m["qp_scaled"][1 + pl])
-                        sc, per = s4[1][1 + pl][qpc % 6], qpc // 6
-                        c = [int(x) for x in lv[cdc + pl * 4: cdc + pl * 4 + 4]]
-                        f = (c[0] + c[1] + c[2] + c[3], c[0] - c[1] + c[2] - c[3],
-                             c[0] + c[1] - c[2] - c[3], c[0] - c[1] - c[2] + c[3])[cb]
-                        for pos in range(16):
-                            if pos == 0:
-                                v = ((f * int(sc[0])) << per) >> 5
-                            elif cbpc == 2:
-                                v = _dq4(lv[cac + pl * 64 + cb * 16 + pos], sc[pos], per)
-                            else:
-                                v = 0
-                            quad[pl][(pos // 8) * 2 + (pos % 4) // 2] += abs(v)
-                    # the kernel's measure: over the block's four lanes, the larger plane sum of each
-                    chroma_sums.append(int(np.maximum(quad[0], quad[1]).sum()))
-
-        def path(coded, sums, blocked):
-            if not coded or blocked or not sums:
-                return None
-            return "packed" if max(sums) <= PK_RES_MAX else "fallback"
-        out.append((path(luma_coded, luma_sums, t8_any), path(chroma_coded, chroma_sums, False)))
-    return out
-
-
+# (which path a wave takes: extremes.wave_paths, shared with the directed extreme-value cases of
+# tests/extremes.py, which place blocks exactly at the bound)
 QM_RANGES = [(20, 40), (44, 51)]
 QM_SEED = 21
 
@@ -156,7 +92,7 @@ def test_guard_coverage(L):
             cfg = synth.default_cfg(L, 3, W3, H3, qp_min=qp[0], qp_max=qp[1])
             n = {"packed": 0, "fallback": 0}
             for i in range(N3):
-                for lu, ch in _wave_paths(synth.picture(L, cfg, i), quant):
+                for lu, ch in wave_paths(synth.picture(L, cfg, i), quant):
                     for pl, kind in (("luma", lu), ("chroma", ch)):
                         if kind:
                             count[(pl, kind)] += 1
