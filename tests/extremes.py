@@ -20,6 +20,9 @@ Families (case names in CASES):
      lines exactly on the alpha / beta / tc / strong-filter thresholds: across MB edges (bS 1, 2, 4,
      each line checked on its own) and, in the d_every cases, across every edge, inner ones included
      (bS 3, Intra_16x16 at high QP, the 8x8 transform), checked by restating the whole loop filter
+  S  strength from motion (tests/extremes_s.py): one-dimensional pictures without residual whose edges
+     are decided by the motion comparison alone, every row of that rule (limits per component, picture
+     identity against ref_idx, both pairings of two lists, slice boundaries) on its thresholds
 tests/test_extremes.py holds the census (each family hits its target, from the inputs and the oracle
 alone) and pins the oracle to the reference decoder on these inputs (tests/golden/extremes.json);
 tests/test_gpu_extremes.py compares the GPU with the oracle.
@@ -1350,12 +1353,14 @@ def one_mb(p: synth.Picture, mi: int) -> synth.Picture:
 
 
 # ---------------------------------------------------------------- D, every edge: inner edges, bS 3, Intra_16x16, 8x8 transform
-def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None):
+def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None, probe=None):
     """8.7 on a whole picture given the bS of every edge segment, in Python integers: per MB in raster
     order the vertical edges left to right, then the horizontal ones, luma and (edges 0 and 2) chroma.
     planes: [Y, Cb, Cr] int arrays, filtered in place.  qp_y / qp_c [H][W]; bsV[by][bx] the bS of the
     vertical edge left of 4x4 block (bx, by), bsH[by][bx] of the horizontal edge above it (0: not
-    filtered).  log(plane, vertical, inner, mb, bS, alpha, beta, tc0, line before): one call per line."""
+    filtered).  log(plane, vertical, inner, mb, bS, alpha, beta, tc0, line before): one call per line.
+    probe(plane, vertical, (x, y) of q0, bS, alpha, beta, indexA, line before): one call per line of
+    every edge the walk meets, those of bS 0 included."""
     for my in range(H):
         for mx in range(W):
             for vertical in (True, False):
@@ -1374,7 +1379,7 @@ def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None):
                         for k in range(size):
                             seg = (k if pl == 0 else 2 * k) // 4
                             bS = int(bsV[4 * my + seg][4 * mx + e]) if vertical else int(bsH[4 * my + e][4 * mx + seg])
-                            if not bS:
+                            if not bS and probe is None:
                                 continue
                             if vertical:
                                 y, x = size * my + k, size * mx + pos
@@ -1382,6 +1387,10 @@ def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None):
                             else:
                                 y, x = size * my + pos, size * mx + k
                                 line = [int(v) for v in img[y - n:y + n, x]]
+                            if probe:
+                                probe(pl, vertical, (x, y), bS, ALPHA[ia], BETA[ib], ia, line)
+                            if not bS:
+                                continue
                             tc0 = TC0[ia][bS - 1] if bS < 4 else 0
                             if log:
                                 log(pl, vertical, e > 0, (mx, my), bS, ALPHA[ia], BETA[ib], tc0, line)
@@ -1591,3 +1600,9 @@ CASES["d_every_h"] = lambda L: build_d_every(L, True)
 D_LINE_CASES = list(D_CASES)                    # lines across MB edges, each checked on its own
 D_EVERY_CASES = ["d_every_v", "d_every_h"]      # every edge, checked by the whole-picture restatement
 D_CASES = D_LINE_CASES + D_EVERY_CASES
+
+# ---------------------------------------------------------------- S: strength from motion
+import extremes_s as _S  # noqa: E402  (the builders need the helpers above)
+
+CASES.update(_S.S_CASES)
+S_CASES = list(_S.S_CASES)

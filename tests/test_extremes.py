@@ -409,3 +409,145 @@ def test_census_d_every_edge(name):
             if bx % 4:
                 pairs |= {frozenset((int(bs[by, bx]), int(bs[by + 1, bx]))) for by in range(bs.shape[0] - 1) if by % 4 != 3}
     assert {frozenset((0, 2)), frozenset((1, 2))} <= pairs, pairs
+
+
+# ---------------------------------------------------------------- census: S
+S_ROWS = {"s_p_v": {1, 2, 3, 4, 5, 6, 7, 8, 13, 14}, "s_p_h": {1, 2, 3, 4, 5, 6, 7, 8, 13, 14},
+          "s_422_v": {1, 2, 3, 4, 5, 6, 7, 8, 14},
+          "s_field_v": {1, 2, 3, 4, 5, 6, 7, 8, 13, 14, 9, 10, 11, "11m", 12},
+          "s_field_h": {1, 2, 3, 4, 5, 6, 7, 8, 13, 14, 9, 10, 11, "11m", 12},
+          "s_b_v": {1, 2, 3, 4, 9, 10, 11, "11m", 12}, "s_b_h": {1, 2, 3, 4, 9, 10, 11, "11m", 12}}
+
+
+@pytest.mark.parametrize("name", [n for n in X.S_CASES if n != "s_mbaff_v"])
+def test_census_s(name):
+    """Strength from motion.  From the inputs and the oracle alone: the reconstruction is
+    one-dimensional; the plain-Python strength derivation (extremes_s.strength_restate) gives every
+    designed segment its designed bS; the loop filter restated from THAT bS equals the oracle's output
+    (which pins the oracle's own derivation to a second statement; the edges of the other direction
+    are inert only until neighbouring segments of one edge are filtered under different bS, so they
+    are restated with everything else rather than asserted idle); every table row has at least 4 live
+    segments (bS 1 would change one of its lines as the walk meets them) and at most 1 designed
+    segment in 20 is dead; both polarities of every signed difference occur; the B cases hold every
+    single-list row under both dispatches of inter4_one_list."""
+    import extremes_s as S
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    rows_live, rows_all, dead, total = {}, {}, 0, 0
+    signs, row8, dispatch = set(), set(), {}
+    for p, d in zip(c.pics, c.info["design"]):
+        W, H = p.cfg.width_mbs, p.cfg.height_mbs
+        rec, full = O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs)
+        for k in range(3):
+            a = rec[k].T if hz else rec[k]
+            assert (a == a[0]).all(), (name, k)
+        bsV, bsH = S.strength_restate(p)
+        mine = bsH.T if hz else bsV
+        assert set(np.unique(bsV)) | set(np.unique(bsH)) <= {0, 1}
+        for s in d["segs"]:
+            assert int(mine[s["r"], s["c"]]) == s["bs"], (name, p.index, s)
+        live = {}
+
+        def probe(pl, vertical, xy, bS, alpha, beta, ia, line):
+            if vertical != hz and pl == 0:
+                key = (xy[1] // 4, xy[0] // 4) if hz else (xy[0] // 4, xy[1] // 4)
+                live[key] = live.get(key, False) or X.filter_line(line, alpha, beta, 1, False, X.TC0[ia][0]) != line
+        planes = [a.astype(np.int64) for a in rec]
+        qp_y = np.full((H, W), d["qp"])
+        X.deblock_restate(planes, W, H, qp_y, np.full((H, W), X.QP_C[d["qp"]]), bsV, bsH, 0, 0, probe=probe)
+        for k in range(1 if c.chroma_format == 2 else 3):       # (the restatement's chroma is 4:2:0)
+            assert np.array_equal(planes[k], full[k]), (name, p.index, k, np.argwhere(planes[k] != full[k])[:3])
+        assert not np.array_equal(full[0], rec[0])
+        one = S.one_list_waves(p)
+        for s in d["segs"]:
+            lv = live[(s["c"], s["r"])]
+            total, dead = total + 1, dead + (not lv)
+            rows_all[s["row"]] = rows_all.get(s["row"], 0) + 1
+            rows_live[s["row"]] = rows_live.get(s["row"], 0) + lv
+            if lv:
+                signs.add((s["row"], s["sx"], s["sy"], s["bs"]))
+                if s["row"] == 8:
+                    row8.add((s["same_idx"], s["same_pic"], s["bs"]))
+                x4, y4 = (s["r"], s["c"]) if hz else (s["c"], s["r"])
+                if s["single"] and s["row"] in (1, 2, 3, 4) and int(p.ref_idx[1, y4, x4]) < 0:
+                    dispatch.setdefault(s["row"], set()).add(one[((y4 // 4) * W + x4 // 4) // 4])
+    assert set(rows_all) == S_ROWS[name], set(rows_all) ^ S_ROWS[name]
+    assert all(rows_live[r] >= 4 for r in rows_all), rows_live
+    assert dead * 20 <= total, (dead, total, {r: rows_all[r] - rows_live[r] for r in rows_all})
+    if name.startswith("s_field"):
+        assert c.info["lim"] == 2 and {int(p.pic["structure"][0]) for p in c.pics} == {A.TOP_FIELD, A.BOTTOM_FIELD}
+        # |dmvy| 2 and 3 are far in a field; the other parity of one slot is another picture
+        assert {b for r, _, sy, b in signs if r == 3 and sy} == {0, 1} and rows_live[7] >= 4
+    for sg in (1, -1):
+        assert {(2, sg, 0, 0), (2, sg, 0, 1), (3, 0, sg, 0), (3, 0, sg, 1)} <= signs, signs      # +-(limit - 1) -> 0, +-limit -> 1
+        for sh in (1, -1):
+            assert {(4, sg, sh, 0), (4, sg, sh, 1)} <= signs
+    if name.startswith("s_b"):
+        assert all(dispatch.get(r) == {False, True} for r in (1, 2, 3, 4)), dispatch
+    if name.startswith(("s_b", "s_field")):
+        assert {w for p in c.pics for w in p.slices["wp_mode"]} == {0, 1}
+        for r in (9, 10, 11, 12):
+            assert {b for rr, _, _, b in signs if rr == r} == {0, 1}, r
+    if not name.startswith("s_b"):
+        # row 8: one ref_idx number naming two pictures -> 1; two numbers naming one picture -> by vector
+        assert {(True, False, 1), (False, True, 0), (False, True, 1)} <= row8, row8
+        assert {b for rr, _, _, b in signs if rr == 5} == {0, 1} and {b for rr, _, _, b in signs if rr == 6} == {0, 1}
+
+
+def test_census_s_mbaff():
+    """MBAFF, vertical edges.  Every block column is uniform along y (asserted on the inputs: MB kind,
+    ref_idx, vectors), so every horizontal edge compares identical motion of one kind and is idle, and
+    the oracle's output is one-dimensional like its reconstruction (asserted).  One row, its vertical
+    edges filtered left to right under the restated bS (extremes_s.strength_restate_mbaff_v), is
+    therefore the whole loop filter: it equals every row of the oracle's output.  Rows 1-7 are live
+    between two frame MBs and between two field MBs, row 15 between a frame and a field MB."""
+    import extremes_s as S
+    c = X.build("s_mbaff_v")
+    live_rows, dead, total = {}, 0, 0
+    for p, d in zip(c.pics, c.info["design"]):
+        assert int(p.pic["structure"][0]) == A.MBAFF_FRAME
+        W, H = p.cfg.width_mbs, p.cfg.height_mbs
+        for a in (p.ref_idx, p.mv, p.mbs["flags"].reshape(H, W), p.mbs["slice"].reshape(H, W)):
+            assert (a == a[..., :1, :]).all()                   # uniform along y
+        assert {int(f) & A.MBF_FIELD for f in p.mbs["flags"]} == {0, A.MBF_FIELD}
+        rec, full = O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs)
+        assert all((a == a[0]).all() for a in rec) and all((a == a[0]).all() for a in full)
+        bsV = S.strength_restate_mbaff_v(p)
+        assert (bsV == bsV[0]).all()
+        for s in d["segs"]:
+            assert int(bsV[0, s["c"]]) == s["bs"], (p.index, s)
+        qp, qpc = d["qp"], X.QP_C[d["qp"]]
+        rows = [[int(v) for v in rec[k][0]] for k in range(3)]
+        live = {}
+        for x4 in range(1, 4 * W):
+            bS = int(bsV[0, x4])
+            for pl in range(3):
+                if pl and x4 & 1:
+                    continue
+                n, x, q = (4, 4 * x4, qp) if pl == 0 else (2, 2 * x4, qpc)
+                line = rows[pl][x - n:x + n]
+                if pl == 0:
+                    live[x4] = X.filter_line(line, X.ALPHA[q], X.BETA[q], 1, False, X.TC0[q][0]) != line
+                if bS:
+                    rows[pl][x - n:x + n] = X.filter_line(line, X.ALPHA[q], X.BETA[q], bS, pl > 0, X.TC0[q][bS - 1])
+        for k in range(3):
+            assert (full[k] == np.array(rows[k], np.uint8)).all(), (p.index, k)
+        assert rows[0] != [int(v) for v in rec[0][0]]
+        for s in d["segs"]:
+            total, dead = total + 4 * H, dead + (0 if live[s["c"]] else 4 * H)
+            if live[s["c"]]:
+                key = (s["row"], s["field"])
+                live_rows.setdefault(key, set()).add((s["sx"], s["sy"], s["bs"]))
+    assert dead * 20 <= total, (dead, total)
+    for row in range(1, 8):
+        for fld in (False, True):
+            if (row, fld) == (7, False):
+                assert {b for _, _, b in live_rows[(row, fld)]} == {1}      # another frame
+                continue
+            want = {1: {0}, 7: {1}}.get(row, {0, 1})
+            assert {b for _, _, b in live_rows[(row, fld)]} == want, (row, fld)
+    assert {b for _, _, b in live_rows[(15, False)]} == {1} and {b for _, _, b in live_rows[(15, True)]} == {1}
+    for fld in (False, True):
+        for sg in (1, -1):
+            assert {(sg, 0, 0), (sg, 0, 1)} <= live_rows[(2, fld)] and {(0, sg, 0), (0, sg, 1)} <= live_rows[(3, fld)]
+            assert any(sx == sg and b == 0 for sx, _, b in live_rows[(4, fld)]) and any(sy == sg and b == 1 for _, sy, b in live_rows[(4, fld)])

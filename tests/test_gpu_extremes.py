@@ -19,8 +19,9 @@ from test_gpu_inter_residual import DEBLOCKS, _first_diff
 
 pytestmark = pytest.mark.gpu
 
-ALL_SCHEDULES = X.D_CASES + ["w_explicit_b_flat"]       # the D cases and one B case: all four schedules
-SPECIAL = {"x_422_p"}                                    # its own context (chroma_format_idc 2)
+S_PLAIN = [n for n in X.S_CASES if n not in ("s_422_v", "s_mbaff_v")]
+ALL_SCHEDULES = X.D_CASES + ["w_explicit_b_flat"] + S_PLAIN      # the D and S cases and one B case: all four schedules
+SPECIAL = {"x_422_p", "s_422_v"}                         # their own context (chroma_format_idc 2)
 
 
 @pytest.fixture(scope="module")
@@ -66,16 +67,17 @@ def _batch_vs_oracle(dec, c, deblocks):
 
 @pytest.mark.parametrize("name", [n for n in X.CASES if n not in ALL_SCHEDULES and n not in SPECIAL])
 def test_gpu_extreme_case(dec, name):
-    """R / M / W cases and the MBAFF case under the band walk."""
+    """R / M / W cases and the MBAFF cases under the band walk."""
     c = X.build(name)
-    if name == "x_mbaff_p":
+    if name in ("x_mbaff_p", "s_mbaff_v"):
         assert all(int(p.pic["structure"][0]) == A.MBAFF_FRAME for p in c.pics)      # k_mbaff's launch sequence
     _batch_vs_oracle(dec, c, (A.DBG_DEBLOCK_ROWS,))
 
 
 @pytest.mark.parametrize("name", ALL_SCHEDULES)
 def test_gpu_extreme_case_all_schedules(dec, name):
-    """The deblocking-threshold cases and one B case under all four deblocking schedules."""
+    """The deblocking-threshold cases, the strength-from-motion cases and one B case under all four
+    deblocking schedules."""
     _batch_vs_oracle(dec, X.build(name), DEBLOCKS)
 
 
@@ -84,10 +86,17 @@ def test_gpu_extreme_422(dec422):
     _batch_vs_oracle(dec422, X.build("x_422_p"), (A.DBG_DEBLOCK_ROWS,))
 
 
-@pytest.mark.parametrize("name", ["r2_over", "m2_borders_p"])
+def test_gpu_extreme_s_422(dec422):
+    """Strength from motion through k_chroma422, which filters its chroma with the luma strengths,
+    under the three schedules the 4:2:2 path has."""
+    _batch_vs_oracle(dec422, X.build("s_422_v"), (A.DBG_DEBLOCK_MB, A.DBG_DEBLOCK_ROWS, A.DBG_DEBLOCK_SPLIT))
+
+
+@pytest.mark.parametrize("name", ["r2_over", "m2_borders_p", "s_b_v"])
 def test_gpu_extreme_streaming(dec, name):
     """The streaming API (picture_begin / mb_submit / picture_end) stages its inputs on a host path
-    of its own: the over-bound residuals and the border-crossing vectors through it."""
+    of its own: the over-bound residuals, the border-crossing vectors and the two-list motion of the
+    strength cases through it."""
     c = X.build(name)
     for s, (y, u, v) in enumerate(c.refs):
         dec.set_ref(s, y, u, v)
