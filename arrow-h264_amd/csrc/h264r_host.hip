@@ -23,6 +23,7 @@
 
 #include "h264r.h"
 #include "launch_cfg.h"
+#include "wp_math.h"
 
 #ifndef H264R_WALK_ROWS
 #define H264R_WALK_ROWS 8       // k_intra_pic: MB rows per band = waves per workgroup (k_picture.hip)
@@ -164,6 +165,8 @@ struct h264r_ctx {
         std::vector<h264r_slice> h_slices;
         h264r_pic h_pic{};
         h264r_quant h_quant{};
+        h264r_field_poc h_fpoc{};                  // h264r_picture_field_pocs: this picture's record
+        bool has_fpoc = false;
         std::vector<uint8_t> seen;
         uint8_t* out = nullptr; size_t c_out = 0;   // pinned planes Y | Cb | Cr, then the error word
         hipEvent_t done = nullptr;                 // its uploads, launches and readback
@@ -180,6 +183,7 @@ struct h264r_ctx {
     h264r_slice* d_slices = nullptr; size_t c_slices = 0;
     h264r_pic* d_pic = nullptr; size_t c_pic = 0;
     h264r_quant* d_quant = nullptr; size_t c_quant = 0;
+    h264r_field_poc* d_fpoc = nullptr; size_t c_fpoc = 0;
     uint8_t* d_out = nullptr; size_t c_out = 0;
     // per-batch scratch of the launch sequence
     Scratch sc;
@@ -222,6 +226,11 @@ const char* h264r_strerror(int s)
     case H264R_ENODEVICE: return "no gfx950 device";
     default: return "unknown status";
     }
+}
+
+int h264r_implicit_w1(int cur_poc, int poc0, int poc1, int long_term0, int long_term1)
+{
+    return h264r::wp_implicit_w1(cur_poc, poc0, poc1, long_term0, long_term1);
 }
 
 int h264r_device_count(void)
@@ -391,6 +400,7 @@ int h264r_destroy(h264r_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (int s = 0; s < H264R_MAX_SLOTS; ++s) if (c->slot[s][0]) (void)hipFree(c->slot[s][0]);
     void* bufs[] = {c->d_ref_planes, c->d_err, c->d_mbs, c->d_levels, c->d_mv, c->d_ref, c->d_slices, c->d_pic, c->d_quant, c->d_out,
+                    c->d_fpoc,
                     c->d444_mbs, c->d444_slices, c->d444_quant, c->d444_refs, c->d444_chroma};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (auto& p : c->sp) {
@@ -1097,7 +1107,19 @@ int h264r_picture_begin(h264r_ctx* c, int w, int h, const h264r_pic* pic, const 
     P.h_pic = *pic;
     P.h_quant = *quant;
     P.seen.assign(n, 0);
+    P.has_fpoc = false;                                        // a record covers one picture
     c->in_pic = true;
+    return H264R_OK;
+}
+
+int h264r_picture_field_pocs(h264r_ctx* c, const h264r_field_poc* rec)
+{
+    if (!c) return H264R_EINVAL;
+    if (!c->in_pic) return H264R_ESTATE;
+    auto& P = c->sp[c->sp_fill];
+    if (!rec || P.h_pic.structure != H264R_MBAFF_FRAME) return H264R_EINVAL;
+    P.h_fpoc = *rec;
+    P.has_fpoc = true;
     return H264R_OK;
 }
 
@@ -1154,11 +1176,12 @@ int h264r_picture_end_async(h264r_ctx* c, int keep_slot)
     const int mbaff = P.h_pic.structure == H264R_MBAFF_FRAME;
     if (P.h_pic.structure < H264R_FRAME || P.h_pic.structure > H264R_MBAFF_FRAME) return H264R_EINVAL;
     if (mbaff) {
-        // MBAFF (include/h264r.h): 4:2:0, MB pairs, no implicit weights (k_mbaff_inter flags the
-        // same cases, and an SP slice's 8x8 transforms and QsC >= 6, on the device: h264r_picture_wait)
+        // MBAFF (include/h264r.h): 4:2:0, MB pairs, implicit weights only with the picture's field POCs
+        // (k_mbaff_inter flags the same cases, and an SP slice's 8x8 transforms and QsC >= 6, on the
+        // device: h264r_picture_wait)
         if (P.ph & 1) return H264R_EINVAL;
         for (const h264r_slice& sl : P.h_slices)
-            if (sl.wp_mode == 2) return H264R_EUNSUPPORTED;
+            if (sl.wp_mode == 2 && !P.has_fpoc) return H264R_EUNSUPPORTED;
         for (size_t a = 0; a < P.h_mbs.size(); a += 1) {
             const size_t top = ((a / P.pw) & ~(size_t)1) * P.pw + a % P.pw;
             if ((P.h_mbs[a].flags ^ P.h_mbs[top].flags) & H264R_MBF_FIELD) return H264R_EINVAL;   // one flag per pair
@@ -1191,7 +1214,8 @@ int h264r_picture_end_async(h264r_ctx* c, int keep_slot)
     if ((st = dev_resize(&c->d_mbs, &c->c_mbs, n)) || (st = dev_resize(&c->d_levels, &c->c_levels, P.h_levels.size())) ||
         (st = dev_resize(&c->d_mv, &c->c_mv, P.h_mv.size())) || (st = dev_resize(&c->d_ref, &c->c_ref, P.h_ref.size())) ||
         (st = dev_resize(&c->d_slices, &c->c_slices, P.h_slices.size())) || (st = dev_resize(&c->d_pic, &c->c_pic, 1)) ||
-        (st = dev_resize(&c->d_quant, &c->c_quant, 1)) || (st = dev_resize(&c->d_out, &c->c_out, ys + 2 * cs)))
+        (st = dev_resize(&c->d_quant, &c->c_quant, 1)) || (st = dev_resize(&c->d_out, &c->c_out, ys + 2 * cs)) ||
+        (P.has_fpoc && (st = dev_resize(&c->d_fpoc, &c->c_fpoc, 1))))
         return st;
     if (P.c_out < ys + 2 * cs + 16) {
         if (P.out) (void)hipHostFree(P.out);
@@ -1208,12 +1232,14 @@ int h264r_picture_end_async(h264r_ctx* c, int keep_slot)
     HIP_OK(hipMemcpyAsync(c->d_slices, P.h_slices.data(), P.h_slices.size() * sizeof(h264r_slice), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(c->d_pic, &P.h_pic, sizeof(h264r_pic), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(c->d_quant, &P.h_quant, sizeof(h264r_quant), hipMemcpyHostToDevice, s));
+    if (P.has_fpoc) HIP_OK(hipMemcpyAsync(c->d_fpoc, &P.h_fpoc, sizeof(h264r_field_poc), hipMemcpyHostToDevice, s));
     h264r_batch b{};
     b.num_pics = 1; b.width_mbs = P.pw; b.height_mbs = P.ph; b.slice_stride = (int)P.h_slices.size();
     b.mbs = c->d_mbs; b.levels = c->d_levels; b.mv = c->d_mv; b.ref_idx = c->d_ref; b.slices = c->d_slices;
     b.pics = c->d_pic; b.quant = c->d_quant; b.ref_planes = c->d_ref_planes;
     b.out_y = c->d_out; b.out_u = c->d_out + ys; b.out_v = c->d_out + ys + cs;
     b.mbaff = mbaff;
+    b.field_poc = P.has_fpoc ? c->d_fpoc : nullptr;
     if ((st = run_batch(c, b, s, 0, b.height_mbs))) return st;
     if (keep_slot >= 0) {
         if ((st = ensure_slot(c, keep_slot, P.pw, frame_h))) return st;

@@ -34,12 +34,16 @@
 // along the block's prediction direction) and SP slices (mb_sp: inverse_transform_sp on the MB's
 // field or frame prediction; intra MBs as usual; an SP MB counts as intra for bS) are decoded; the
 // CPU oracle refuses both in MBAFF frames, so tests/golden/mbaff_ext.json pins them to the
-// reference itself.  Not decoded: implicit weights, SI, an SP slice's 8x8 transforms or QsC >= 6,
+// reference itself.  Implicit weights (wp_mode 2) are decoded when the batch carries the pictures'
+// field POCs (h264r_batch.field_poc): a frame MB takes the slice's implicit_w1 table, a field MB
+// derives its weight from the POCs of the two fields it reads and of its own parity (wp_math.h).
+// Not decoded: implicit weights without that record, SI, an SP slice's 8x8 transforms or QsC >= 6,
 // a pair whose MBs disagree on the field flag, a picture that is no MBAFF frame.  k_mbaff_inter
 // sets the context's error word for each of them (h264r_check reports it): a device-resident
 // batch reaches no host check.
 #include "device_common.h"
 #include "sp_math.h"
+#include "wp_math.h"
 
 namespace h264r {
 namespace {
@@ -55,6 +59,7 @@ struct MPic {
     uint8_t* out[3];
     int wmb, hmb, W4, mplane;
     int cip;
+    const h264r_field_poc* fpoc;   // the picture's field POCs (implicit weights of field MBs), or nullptr
 };
 
 DEV MPic mpic(const h264r_batch& b, int p)
@@ -73,6 +78,7 @@ DEV MPic mpic(const h264r_batch& b, int p)
     P.out[1] = b.out_u + (size_t)p * nmb * 64;
     P.out[2] = b.out_v + (size_t)p * nmb * 64;
     P.cip = b.pics[p].constrained_intra_pred;
+    P.fpoc = b.field_poc ? b.field_poc + p : nullptr;
     return P;
 }
 
@@ -431,6 +437,36 @@ DEV int chroma_mc(const uint8_t* img, int W, int pitch, int H, int xi, int yi, i
 
 DEV int rshift_rnd(int x, int a) { return a > 0 ? (x + (1 << (a - 1))) >> a : x * (1 << -a); }   // inter_prediction.cc:35-38
 
+// weight1 of a field MB's block predicted from field refIdx rr0 of list 0 and rr1 of list 1 (both
+// >= 0), by the picture's field POCs (:112-137): each list's slot and field as motion compensation
+// finds them, the slot bounded as there (a list without a usable slot is flagged there: 32 here)
+DEV int field_w1(const h264r_field_poc& f, const h264r_slice& sl, int rr0, int rr1, int mbot)
+{
+    const int s0 = (rr0 >> 1) < H264R_MAX_REFS ? sl.ref_slot[0][rr0 >> 1] : -1;
+    const int s1 = (rr1 >> 1) < H264R_MAX_REFS ? sl.ref_slot[1][rr1 >> 1] : -1;
+    if (s0 < 0 || s0 >= H264R_MAX_SLOTS || s1 < 0 || s1 >= H264R_MAX_SLOTS) return 32;
+    const int b0 = (rr0 & 1) != mbot, b1 = (rr1 & 1) != mbot;              // get_ref_pic
+    return wp_implicit_w1(f.cur_poc[mbot], f.slot_poc[s0][b0], f.slot_poc[s1][b1], (f.long_term[b0] >> s0) & 1,
+                          (f.long_term[b1] >> s1) & 1);
+}
+
+// One implicitly weighted sample (wp_mode 2, bi_prediction :112-153) from the two lists' predictions v0
+// and v1: rr0 / rr1 the block's refIdx per list as stored (a field MB's count fields).  A frame MB takes
+// the slice's table of frame-POC weights, a field MB derives its weight from the record f.  Kept out of
+// line: inter_sample is inlined four times into k_mbaff_inter, whose time follows its code size (DESIGN.md
+// section 4g) -- pictures without implicit weights pay for one call site each, not for the derivation.
+__device__ __attribute__((noinline)) int implicit_bipred(const h264r_field_poc* f, const h264r_slice& sl, int rr0, int rr1,
+                                                         bool fmb, int mbot, int pl, int v0, int v1)
+{
+    int w1 = 32;
+    if (!fmb) {                                                            // the frame POCs' table
+        if (rr0 < H264R_MAX_REFS && rr1 < H264R_MAX_REFS) w1 = sl.implicit_w1[rr0][rr1];
+    } else if (f) {                                                        // the POCs of the two fields read
+        w1 = field_w1(*f, sl, rr0, rr1, mbot);
+    }
+    return clip255(rshift_rnd((64 - w1) * v0 + w1 * v1, (pl ? sl.chroma_log2_wd : sl.luma_log2_wd) + 1));
+}
+
 // the prediction of sample (x, y) of plane pl of inter MB r (inter_pred, mc_prediction,
 // bi_prediction, inter_prediction.cc:53-156, 448-536)
 DEV int inter_sample(const MPic& P, int r, int pl, int x, int y, int* err)
@@ -477,6 +513,9 @@ DEV int inter_sample(const MPic& P, int r, int pl, int x, int y, int* err)
         const int o = (sl.wp_offset[0][rw[0]][pl] + sl.wp_offset[1][rw[1]][pl] + 1) >> 1;
         return clip255(rshift_rnd(w0 * v[0] + w1 * v[1], (pl ? sl.chroma_log2_wd : sl.luma_log2_wd) + 1) + o);
     }
+    if (sl.wp_mode == 2)                                                   // implicit weights :112-139
+        return implicit_bipred(P.fpoc, sl, fmb ? P.ref[idx] : rw[0], fmb ? P.ref[P.mplane + idx] : rw[1], fmb, mbot, pl,
+                               v[0], v[1]);
     return (v[0] + v[1] + 1) >> 1;
 }
 
@@ -967,7 +1006,7 @@ extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, i
     // What this launch sequence does not decode (include/h264r.h H264R_MBAFF_FRAME) is reported in the
     // context's error word, for h264r_check / h264r_picture_wait; the MB is left undecoded.
     const int other = (r / P.wmb) & 1 ? r - P.wmb : r + P.wmb;             // the pair's other MB
-    if (b.pics[pic].structure != H264R_MBAFF_FRAME || sl.wp_mode == 2 || m.mb_type == H264R_SI ||
+    if (b.pics[pic].structure != H264R_MBAFF_FRAME || (sl.wp_mode == 2 && !b.field_poc) || m.mb_type == H264R_SI ||
         sl.slice_type == H264R_SLICE_SI || ((m.flags ^ P.mbs[other].flags) & H264R_MBF_FIELD) ||
         (sp && ((m.flags & H264R_MBF_T8x8) || sl.qs_y > 51 || sl.qs_c[0] < 0 || sl.qs_c[0] >= 6 || sl.qs_c[1] < 0 ||
                 sl.qs_c[1] >= 6))) {

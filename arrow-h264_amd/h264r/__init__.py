@@ -21,7 +21,7 @@ import os
 import numpy as np
 
 from . import _abi as A
-from ._abi import MB_DTYPE, PIC_DTYPE, QUANT_DTYPE, SLICE_DTYPE  # noqa: F401
+from ._abi import FIELD_POC_DTYPE, MB_DTYPE, PIC_DTYPE, QUANT_DTYPE, SLICE_DTYPE  # noqa: F401
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("H264R_LIB") or os.path.join(PKG_DIR, "lib", "libh264r.so")
@@ -68,6 +68,8 @@ def lib() -> C.CDLL:
         "h264r_create": ([C.POINTER(P), I, I, I, I, I], I), "h264r_destroy": ([P], I),
         "h264r_set_ref": ([P, I, P, P, P, I, I], I),
         "h264r_picture_begin": ([P, I, I, P, P, P], I),
+        "h264r_picture_field_pocs": ([P, P], I),
+        "h264r_implicit_w1": ([I, I, I, I, I], I),
         "h264r_mb_submit": ([P, I, P, P, I, P, P], I),
         "h264r_picture_end": ([P, P, P, P, I], I),
         "h264r_picture_end_async": ([P, I], I),
@@ -171,6 +173,12 @@ class Decoder:
             self._h, width_mbs, height_mbs, A.ptr(self._pic), A.ptr(self._slices), A.ptr(self._quant)))
         self._dims = (width_mbs, height_mbs)
 
+    def field_pocs(self, rec: np.ndarray) -> None:
+        """h264r_picture_field_pocs: the field POCs (one FIELD_POC_DTYPE record) of the MBAFF picture
+        being staged, from which its field MBs' implicit weights are derived."""
+        r = np.ascontiguousarray(rec, FIELD_POC_DTYPE).reshape(1)
+        _check("h264r_picture_field_pocs", self._L.h264r_picture_field_pocs(self._h, A.ptr(r)))
+
     def decode(self, mb_addr: int, mb: np.ndarray, levels: np.ndarray, mv: np.ndarray,
                ref_idx: np.ndarray) -> None:
         """Decoder::decode(mb): mb is one MB_DTYPE record, levels its level block,
@@ -214,15 +222,18 @@ class Decoder:
 
     # -- convenience ----------------------------------------------------------------
     def decode_picture(self, p, refs=None, keep_slot: int = -1, no_deblock: bool = False,
-                       intra_walk: bool = False, debug: int = 0):
+                       intra_walk: bool = False, debug: int = 0, field_pocs=None):
         """Submit every MB of a synth.Picture (raster order) and return its planes
-        (debug: further h264r_set_debug flags for this picture)."""
+        (debug: further h264r_set_debug flags for this picture; field_pocs: the FIELD_POC_DTYPE
+        record of an MBAFF picture with implicit weights)."""
         from .mbview import iter_mbs
         if refs is not None:
             for s, (y, u, v) in enumerate(refs):
                 self.set_ref(s, y, u, v)
         W, H = p.cfg.width_mbs, p.cfg.height_mbs
         self.init(W, H, p.pic, p.slices)
+        if field_pocs is not None:
+            self.field_pocs(field_pocs)
         for addr, rec, lv, mv, rr in iter_mbs(p):
             self.decode(addr, rec, lv, mv, rr)
         self.set_debug((A.DBG_NO_DEBLOCK if no_deblock else 0) | (A.DBG_INTRA_WALK if intra_walk else 0) | debug)

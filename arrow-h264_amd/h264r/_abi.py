@@ -16,7 +16,7 @@ DBG_WAIT_TEST = 32
 DBG_OVERLAP = 64
 DBG_DEBLOCK_SPLIT = 128
 MAX_REFS, MAX_SLOTS, MAX_SLICES = 16, 32, 256
-ABI_VERSION = 4
+ABI_VERSION = 5
 FRAME, TOP_FIELD, BOTTOM_FIELD, MBAFF_FRAME = 0, 1, 2, 3   # h264r_pic.structure
 REF_BOTTOM = 0x40                              # ref_slot entry of a field picture: the slot's bottom field
 
@@ -74,6 +74,11 @@ assert QUANT_DTYPE.itemsize == 5760
 PIC_DTYPE = np.dtype([("constrained_intra_pred", "<i4"), ("num_slices", "<i4"),
                       ("poc", "<i4"), ("structure", "<i4")])
 
+# h264r_field_poc: the field POCs of one MBAFF picture (implicit weights of its field MBs)
+FIELD_POC_DTYPE = np.dtype([("cur_poc", "<i4", (2,)), ("slot_poc", "<i4", (MAX_SLOTS, 2)),
+                            ("long_term", "<u4", (2,))])
+assert FIELD_POC_DTYPE.itemsize == 272
+
 
 class SynthCfg(C.Structure):
     _fields_ = [
@@ -108,6 +113,7 @@ class Batch(C.Structure):
         ("pics", C.c_void_p), ("quant", C.c_void_p), ("ref_planes", C.c_void_p),
         ("out_y", C.c_void_p), ("out_u", C.c_void_p), ("out_v", C.c_void_p),
         ("ref_planes_stride", C.c_int64), ("mbaff", C.c_int32), ("colour_plane", C.c_int32),
+        ("field_poc", C.c_void_p),
     ]
 
 

@@ -31,8 +31,9 @@ class DeviceBatch:
         return y, u, v
 
 
-def pack(pictures, quant: np.ndarray):
-    """Concatenate synth.Pictures into host arrays with one shared level pool."""
+def pack(pictures, quant: np.ndarray, field_pocs=None):
+    """Concatenate synth.Pictures into host arrays with one shared level pool (field_pocs: one
+    FIELD_POC_DTYPE record per picture, for MBAFF pictures with implicit weights)."""
     W, H = pictures[0].cfg.width_mbs, pictures[0].cfg.height_mbs
     stride = max(len(p.slices) for p in pictures)
     mbs, lv, mv, rr, sl, pics = [], [], [], [], [], []
@@ -54,9 +55,13 @@ def pack(pictures, quant: np.ndarray):
         sl.append(s)
         pics.append(p.pic)
     q = np.repeat(np.ascontiguousarray(quant, A.QUANT_DTYPE).reshape(1), len(pictures))
+    extra = {}
+    if field_pocs is not None:
+        extra["field_pocs"] = np.concatenate([np.ascontiguousarray(r, A.FIELD_POC_DTYPE).reshape(1) for r in field_pocs])
+        assert len(extra["field_pocs"]) == len(pictures)
     return dict(mbs=np.concatenate(mbs), levels=np.concatenate(lv), mv=np.stack(mv), ref_idx=np.stack(rr),
                 slices=np.concatenate(sl), pics=np.concatenate(pics), quant=q, stride=stride, W=W, H=H,
-                chroma_format=A.idc_of(pictures[0].cfg.chroma_format))
+                chroma_format=A.idc_of(pictures[0].cfg.chroma_format), **extra)
 
 
 def to_device(host: dict, n: int, ref_planes_ptr: int | None, device: str = "cuda") -> DeviceBatch:
@@ -78,6 +83,10 @@ def to_device(host: dict, n: int, ref_planes_ptr: int | None, device: str = "cud
     for k in ("mbs", "levels", "mv", "ref_idx", "slices", "pics", "quant", "out_y", "out_u", "out_v"):
         setattr(b, k, t[k].data_ptr())
     b.ref_planes = ref_planes_ptr
+    if host.get("field_pocs") is not None:              # one record per picture (h264r_batch.field_poc)
+        assert len(host["field_pocs"]) == n
+        t["field_pocs"] = dev(host["field_pocs"])
+        b.field_poc = t["field_pocs"].data_ptr()
     # MBAFF frames take their own launch sequence (include/h264r.h h264r_batch.mbaff)
     b.mbaff = int(bool((host["pics"]["structure"] == A.MBAFF_FRAME).all()))
     return DeviceBatch(b, n, W, H, t, fmt)

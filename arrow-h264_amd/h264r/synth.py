@@ -76,6 +76,17 @@ def refpics(lib: C.CDLL, cfg: A.SynthCfg, nslots: int | None = None):
     return out
 
 
+def field_pocs(lib: C.CDLL, p: Picture) -> np.ndarray:
+    """The FIELD_POC_DTYPE record matching the generator's DPB for an MBAFF picture: slot s holds the
+    fields of POC h264r_synth_slot_poc(s) (top) and that + 1 (bottom), both current fields carry the
+    picture's POC, no field is long-term."""
+    rec = np.zeros(1, A.FIELD_POC_DTYPE)
+    rec["cur_poc"] = int(p.pic["poc"][0])
+    for s in range(A.MAX_SLOTS):
+        rec["slot_poc"][0, s] = (lib.h264r_synth_slot_poc(s), lib.h264r_synth_slot_poc(s) + 1)
+    return rec
+
+
 def algo_bytes(lib: C.CDLL, p: Picture) -> tuple[int, int]:
     r, w = C.c_int64(0), C.c_int64(0)
     st = lib.h264r_synth_algo_bytes(A.ptr(p.mbs), A.ptr(p.ref_idx), p.cfg.width_mbs,

@@ -96,7 +96,7 @@
 extern "C" {
 #endif
 
-#define H264R_ABI_VERSION 4
+#define H264R_ABI_VERSION 5
 
 /* ---- status codes ---------------------------------------------------------- */
 #define H264R_OK               0
@@ -234,19 +234,37 @@ typedef struct h264r_quant {
  * SP slices (QsC < 6, no 8x8 transform; a field MB's prediction is its field prediction; an SP MB counts
  * as intra for bS) and lossless MBs (H264R_MBF_BYPASS, as in frames) are decoded.  These two are pinned by
  * tests/golden/mbaff_ext.json against the reference decoder itself; the CPU oracle does not restate them.
- * 4:2:0 only.  Not decoded: implicit weights (wp_mode 2: a field MB needs per-parity POC weights, which
- * h264r_slice has no room for) and SI MBs.  The streaming API returns H264R_EUNSUPPORTED for wp_mode 2 and
- * H264R_EINVAL for a pair whose MBs disagree on H264R_MBF_FIELD; the kernels flag both on the device as
- * well, with SI MBs and slices, an SP slice's 8x8-transform MBs or QsC >= 6, and a picture of a batch with
- * mbaff set whose structure is not H264R_MBAFF_FRAME: the launch's output is then invalid and h264r_check
- * (h264r_picture_wait for the streaming API) returns H264R_EDEVICE. */
+ * 4:2:0 only.
+ * Implicit weights (wp_mode 2, ABI 5) are decoded when the caller supplies the picture's field POCs, an
+ * h264r_field_poc record (below: h264r_batch.field_poc, h264r_picture_field_pocs):
+ *   - a frame MB takes weight1 from the slice's implicit_w1[refIdxL0][refIdxL1], the frame POCs' table, as
+ *     in a frame picture;
+ *   - a field MB takes the POCs of the two reference FIELDS it predicts from (slot_poc of the list's
+ *     slot, the MB's own parity when refIdx is even) and the current POC of its own parity (cur_poc), and
+ *     the weight is derived on the device (inter_prediction.cc:112-139, h264r_implicit_w1);
+ *   - blocks predicted from one list are not weighted.
+ * Without the record a wp_mode 2 slice is refused as before ABI 5: the streaming API returns
+ * H264R_EUNSUPPORTED, a device-resident batch is flagged on the device.  The record covers one picture; it
+ * does not carry over to the next.  Not decoded: SI MBs.  The streaming API returns H264R_EINVAL for a pair
+ * whose MBs disagree on H264R_MBF_FIELD; the kernels flag that on the device as well, with wp_mode 2
+ * without a record, SI MBs and slices, an SP slice's 8x8-transform MBs or QsC >= 6, and a picture of a
+ * batch with mbaff set whose structure is not H264R_MBAFF_FRAME: the launch's output is then invalid and
+ * h264r_check (h264r_picture_wait for the streaming API) returns H264R_EDEVICE. */
 #define H264R_MBAFF_FRAME   3
 typedef struct h264r_pic {
     int32_t  constrained_intra_pred;  /* pps.constrained_intra_pred_flag */
     int32_t  num_slices;
-    int32_t  poc;                     /* informational (implicit weights are precomputed) */
+    int32_t  poc;                     /* informational (implicit weights are precomputed, or derived from h264r_field_poc) */
     int32_t  structure;               /* H264R_FRAME / H264R_TOP_FIELD / H264R_BOTTOM_FIELD / H264R_MBAFF_FRAME */
 } h264r_pic;
+
+/* Field POCs of one H264R_MBAFF_FRAME picture (ABI 5): what a field MB's implicit weights are derived
+ * from, H264R_MBAFF_FRAME above.  272 bytes. */
+typedef struct h264r_field_poc {
+    int32_t  cur_poc[2];                    /* TopFieldOrderCnt, BottomFieldOrderCnt (inter_prediction.cc:125-126) */
+    int32_t  slot_poc[H264R_MAX_SLOTS][2];  /* top_field->poc, bottom_field->poc of DPB slot s (:116-120) */
+    uint32_t long_term[2];                  /* bit s: that field of slot s is_long_term (:121) */
+} h264r_field_poc;
 
 /* A batch of same-sized pictures whose arrays are already resident on the device.
  * Per-picture strides: MBs W*H records; motion 2*(4H)*(4W) entries; slices
@@ -293,6 +311,8 @@ typedef struct h264r_batch {
                                         Intra_16x16 DC of plane k by the Y intra list (transform.cc:831-
                                         836); the library by plane k's -- the same unless the first
                                         entries of the two intra 4x4 lists differ */
+    const h264r_field_poc* field_poc;/* ABI 5: device array, one record per picture, or NULL = none; read only
+                                        when mbaff is set and a slice has wp_mode 2 (H264R_MBAFF_FRAME above) */
 } h264r_batch;
 
 typedef struct h264r_ctx h264r_ctx;
@@ -312,6 +332,12 @@ int  h264r_quant_init_flat(h264r_quant* q);
  * 8x8 lists (Intra Y, Inter Y, Intra Cb, Inter Cb, Intra Cr, Inter Cr), raster order. */
 int  h264r_quant_init_lists(h264r_quant* q, const int32_t* const qmatrix[12]);
 
+/* ---- implicit weights (bi_prediction, inter_prediction.cc:120-137) ------------------ */
+/* weight1 of a block predicted from (ref0, ref1) in a picture of POC cur_poc, weight0 = 64 - weight1:
+ * what a producer writes into implicit_w1 of a slice, and what the MBAFF kernels derive for a field MB
+ * from an h264r_field_poc record.  32 for td == 0, a long-term reference or a weight outside -64 .. 128. */
+int  h264r_implicit_w1(int cur_poc, int poc0, int poc1, int long_term0, int long_term1);
+
 /* ---- context ------------------------------------------------------------------- */
 /* chroma_format_idc 0 (4:0:0), 1 (4:2:0), 2 (4:2:2) or 3 (4:4:4, above) and bit_depth 8 (other
  * formats: H264R_EUNSUPPORTED). */
@@ -330,6 +356,11 @@ int  h264r_set_ref(h264r_ctx* ctx, int slot, const uint8_t* y, const uint8_t* u,
 int  h264r_picture_begin(h264r_ctx* ctx, int width_mbs, int height_mbs,
                          const h264r_pic* pic, const h264r_slice* slices,
                          const h264r_quant* quant);
+/* The field POCs of the picture being staged (ABI 5): valid between h264r_picture_begin of an
+ * H264R_MBAFF_FRAME picture and its h264r_picture_end[_async]; H264R_ESTATE outside a picture,
+ * H264R_EINVAL for a picture of another structure or a NULL record.  The record is copied (each of the
+ * two staged pictures has its own) and uploaded with the slices; it covers this picture only. */
+int  h264r_picture_field_pocs(h264r_ctx* ctx, const h264r_field_poc* rec);
 /* Decoder::decode(mb) for MB address mb_addr.  `levels` is this MB's compacted
  * level block (n_levels int16), mv/ref_idx are its 16 4x4 entries per list in
  * raster order ([list][16]). */
