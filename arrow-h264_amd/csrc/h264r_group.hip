@@ -27,8 +27,9 @@ namespace {
 // of the segments before it, so that its offset is pre * num_pics * (bytes of one MB row).
 struct SegDev { int32_t r0, r1, pre, peer; };
 
-// One thread moves 8 bytes (MB rows are 256 W / 64 W bytes: multiples of 8).  Grid: x = chunks of
-// one picture's part of a segment, y = picture, z = segment.
+// One thread moves 8 bytes (MB rows are 256 W luma and 0 / 64 W / 128 W / 256 W chroma bytes by the
+// chroma format: multiples of 8).  Grid: x = chunks of one picture's part of a segment, y = picture,
+// z = segment.  rbc == 0 (4:0:0): no chroma bytes, u and v are never touched.
 __global__ void __launch_bounds__(256) k_band_copy(const SegDev* __restrict__ segs, int nk, uint8_t* __restrict__ buf,
                                                    uint8_t* y, uint8_t* u, uint8_t* v, int64_t sy, int64_t sc,
                                                    int64_t rby, int64_t rbc, int unpack)
@@ -102,7 +103,7 @@ struct h264r_group {
     ncclComm_t comm = nullptr;
     h264r_transport t{};
     // plan
-    int W = 0, H = 0, max_pics = 0;
+    int W = 0, H = 0, max_pics = 0, fmt = 1;   // fmt: chroma_format_idc of the planes
     std::vector<SegDev> give, need;      // peers with rows, increasing rank order
     int give_rows = 0, need_rows = 0;
     SegDev* d_segs = nullptr;            // give then need
@@ -110,7 +111,10 @@ struct h264r_group {
     bool host_pinned = false;
     int64_t sent = 0, received = 0, transfers = 0;
 
-    int64_t mbrow() const { return 384LL * W; }
+    // bytes of one MB row of the luma plane / of each chroma plane / of all three
+    int64_t rby() const { return 256LL * W; }
+    int64_t rbc() const { return fmt == 0 ? 0 : fmt == 1 ? 64LL * W : fmt == 2 ? 128LL * W : 256LL * W; }
+    int64_t mbrow() const { return rby() + 2 * rbc(); }
     void free_buffers()
     {
         if (device >= 0) {
@@ -226,7 +230,14 @@ int h264r_group_destroy(h264r_group* g)
 int h264r_group_set_bands(h264r_group* g, int width_mbs, int height_mbs, const int32_t* bands, int mode,
                           int halo_mb_rows, int max_pics)
 {
-    if (!g || width_mbs < 1 || height_mbs < 1 || max_pics < 1 || max_pics > 65535 || !valid_bands(g->nranks, bands))
+    return h264r_group_set_bands_fmt(g, width_mbs, height_mbs, 1, bands, mode, halo_mb_rows, max_pics);
+}
+
+int h264r_group_set_bands_fmt(h264r_group* g, int width_mbs, int height_mbs, int chroma_format_idc,
+                              const int32_t* bands, int mode, int halo_mb_rows, int max_pics)
+{
+    if (!g || width_mbs < 1 || height_mbs < 1 || max_pics < 1 || max_pics > 65535 || !valid_bands(g->nranks, bands) ||
+        chroma_format_idc < 0 || chroma_format_idc > 3)
         return H264R_EINVAL;
     for (int r = 0; r < g->nranks; ++r)
         if (bands[2 * r + 1] > height_mbs) return H264R_EINVAL;
@@ -234,6 +245,7 @@ int h264r_group_set_bands(h264r_group* g, int width_mbs, int height_mbs, const i
     int st = h264r_group_plan(g->nranks, g->rank, bands, mode, halo_mb_rows, need.data(), give.data());
     if (st != H264R_OK) return st;
     g->free_buffers();
+    g->fmt = chroma_format_idc;
     g->W = width_mbs;
     g->H = height_mbs;
     g->max_pics = max_pics;
@@ -288,12 +300,13 @@ int h264r_group_set_bands(h264r_group* g, int width_mbs, int height_mbs, const i
 static void host_copy(const h264r_group* g, const std::vector<SegDev>& segs, int nk, uint8_t* buf, uint8_t* const pl[3],
                       const int64_t stride[3], bool unpack)
 {
-    const int64_t rb[3] = {256LL * g->W, 64LL * g->W, 64LL * g->W};
+    const int64_t rb[3] = {g->rby(), g->rbc(), g->rbc()};
     for (const SegDev& s : segs) {
         const int64_t rows = s.r1 - s.r0;
         uint8_t* seg = buf + (int64_t)s.pre * nk * g->mbrow();
         for (int i = 0; i < nk; ++i)
             for (int k = 0; k < 3; ++k) {
+                if (!rb[k]) continue;                                  // 4:0:0: no chroma planes
                 uint8_t* p = pl[k] + i * stride[k] + s.r0 * rb[k];
                 const int64_t n = rows * rb[k];
                 if (unpack) memcpy(p, seg, n);
@@ -307,9 +320,14 @@ int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, u
                          int64_t stride_c, void* stream)
 {
     if (!g || !g->max_pics) return g ? H264R_ESTATE : H264R_EINVAL;
-    const int64_t W = g->W, H = g->H;
-    if (num_pics < 1 || num_pics > g->max_pics || !y || !u || !v || stride_y < 256 * W * H || stride_c < 64 * W * H)
+    const int64_t H = g->H, rby = g->rby(), rbc = g->rbc();
+    if (num_pics < 1 || num_pics > g->max_pics || !y || stride_y < rby * H) return H264R_EINVAL;
+    if (!rbc) {                             // 4:0:0: no chroma planes, u / v / stride_c are not looked at
+        u = v = nullptr;
+        stride_c = 0;
+    } else if (!u || !v || stride_c < rbc * H) {
         return H264R_EINVAL;
+    }
     // k_band_copy moves 8-byte words
     if (g->device >= 0 && (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v | (uint64_t)stride_y | (uint64_t)stride_c) & 7))
         return H264R_EINVAL;
@@ -326,7 +344,7 @@ int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, u
         const int64_t per8 = (int64_t)rows * mbrow / 8 / (int64_t)nseg + 1;      // average 8-byte units per picture segment
         const int gx = (int)std::min<int64_t>(64, (per8 + 255) / 256);
         hipLaunchKernelGGL(k_band_copy, dim3(gx, nk, (unsigned)nseg), dim3(256), 0, s, segs, nk, buf, y, u, v, stride_y,
-                           stride_c, 256 * W, 64 * W, unpack);
+                           stride_c, rby, rbc, unpack);
         return hipGetLastError();
     };
 

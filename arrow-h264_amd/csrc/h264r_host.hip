@@ -39,9 +39,9 @@ extern "C" __global__ void k_untile(h264r_batch b, int2 rows, const uint8_t* rec
 extern "C" __global__ void k_c422_inter(h264r_batch b, int2 rows, int* err);
 extern "C" __global__ void k_c422_intra(h264r_batch b, int2 rows, int* err);
 extern "C" __global__ void k_c422_db(h264r_batch b, const h264r::DbInfo* dbinfo, int2 rows, int* err);
-extern "C" __global__ void k_mbaff_inter(h264r_batch b, int* err);
-extern "C" __global__ void k_mbaff_intra(h264r_batch b, int diag, int* err);
-extern "C" __global__ void k_mbaff_deblock(h264r_batch b, int diag, int* err);
+extern "C" __global__ void k_mbaff_inter(h264r_batch b, int2 rows, int* err);
+extern "C" __global__ void k_mbaff_intra(h264r_batch b, int diag, int2 rows, int* err);
+extern "C" __global__ void k_mbaff_deblock(h264r_batch b, int diag, int2 rows, int* err);
 extern "C" __global__ void k_intra_pic(h264r_batch b, int* sync, int* err, const uint16_t* lvl, int lmax, int2 rows,
                                       int gstep, uint8_t* recon, const int* pband);
 extern "C" __global__ void k_level(h264r_batch b, uint16_t* lvl, int* lvsync, int* lcount, int2 rows, int deep_cut,
@@ -921,29 +921,34 @@ static int run_422(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, 
 // MBAFF frames (include/h264r.h H264R_MBAFF_FRAME, k_mbaff.hip): I_PCM and inter MBs in one launch,
 // then the intra MBs and the loop filter each as one launch per anti-diagonal d = x + 2 y of the
 // MB-pair grid (a pair's neighbours -- and the pairs its filtering modifies -- lie on earlier
-// diagonals).  Whole pictures only.
+// diagonals).  A band [row0, row1) is made of whole pairs (even rows): the grids cover its MBs /
+// pair rows and the diagonals run over its pair rows only, 2 py0 .. W - 1 + 2 (py1 - 1); the whole
+// picture is the band [0, height_mbs).  The band's contract is k_mbaff.hip's: it starts where the
+// top edge is not filtered, or k_mbaff_deblock flags the error word (the launch still drains).
 static int run_mbaff(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, int row1)
 {
     if (c->fmt != 1) return H264R_EUNSUPPORTED;
-    if ((b.height_mbs & 1) || row0 != 0 || row1 != b.height_mbs) return H264R_EINVAL;
-    const int P = b.num_pics, W = b.width_mbs, HP = b.height_mbs / 2, ndiag = W + 2 * (HP - 1);
+    if ((b.height_mbs & 1) || (row0 & 1) || (row1 & 1)) return H264R_EINVAL;
+    const int P = b.num_pics, W = b.width_mbs, HP = (row1 - row0) / 2;
+    const int d0 = row0, d1 = W + row1 - 2;                    // the band's diagonals [d0, d1)
+    const int2 rows = make_int2(row0, row1);
     Timed whole(c, 3, s);
     if (c->timing) c->timed_launches++;
     {
         Timed t(c, 0, s);
-        hipLaunchKernelGGL(k_mbaff_inter, dim3((unsigned)((size_t)P * W * b.height_mbs)), dim3(256), 0, s, b, c->d_err);
+        hipLaunchKernelGGL(k_mbaff_inter, dim3((unsigned)((size_t)P * W * (row1 - row0))), dim3(256), 0, s, b, rows, c->d_err);
         HIP_OK(hipGetLastError());
     }
     {
         Timed t(c, 1, s);
-        for (int d = 0; d < ndiag; ++d)
-            hipLaunchKernelGGL(k_mbaff_intra, dim3((unsigned)(P * HP)), dim3(256), 0, s, b, d, c->d_err);
+        for (int d = d0; d < d1; ++d)
+            hipLaunchKernelGGL(k_mbaff_intra, dim3((unsigned)(P * HP)), dim3(256), 0, s, b, d, rows, c->d_err);
         HIP_OK(hipGetLastError());
     }
     if (!((c->debug | knobs().debug) & H264R_DBG_NO_DEBLOCK)) {
         Timed t(c, 2, s);
-        for (int d = 0; d < ndiag; ++d)
-            hipLaunchKernelGGL(k_mbaff_deblock, dim3((unsigned)(P * HP)), dim3(64), 0, s, b, d, c->d_err);
+        for (int d = d0; d < d1; ++d)
+            hipLaunchKernelGGL(k_mbaff_deblock, dim3((unsigned)(P * HP)), dim3(64), 0, s, b, d, rows, c->d_err);
         HIP_OK(hipGetLastError());
     }
     return H264R_OK;

@@ -30,6 +30,13 @@
 // This is the MBAFF format's own launch sequence: the frame / field-picture path (k_inter4r,
 // k_intra_levels, k_deblock2) keeps its layout.  4:2:0 only.
 //
+// Every kernel takes the band rows = [row0, row1) of MB rows (both even: whole pairs) it decodes
+// (h264r_decode_batch_rows): the grids cover the band's MBs / pair rows only, and nothing outside
+// the band is written.  A band that starts below row 0 starts where the top edge is not filtered
+// (idc 1, or a slice edge with idc 2): k_mbaff_deblock neither filters nor stores the rows above
+// its first pair row -- they are another rank's -- and flags the error word when a pair there has
+// its top edge's flag set, as k_deblock / k_deblock2 do for frame bands.
+//
 // Lossless MBs (H264R_MBF_BYPASS: mb_residual takes the levels as the residual and accumulates them
 // along the block's prediction direction) and SP slices (mb_sp: inverse_transform_sp on the MB's
 // field or frame prediction; intra MBs as usual; an SP MB counts as intra for bS) are decoded; the
@@ -874,8 +881,9 @@ DEV int bs_hor(const MPic& P, int r, int e, int x4, bool f4)
 }
 
 // Deblock::strength's edge flags (deblock.cc:230-278) of MB r: bit 0..3 ver luma, 4..7 hor luma,
-// the chroma edges 0 / 1 (4:2:0) follow the luma ones, bit 8 filterHorEdgeFlag[.][4]
-DEV void edge_flags(const MPic& P, int r, DbLds& D, int h)
+// the chroma edges 0 / 1 (4:2:0) follow the luma ones, bit 8 filterHorEdgeFlag[.][4].  row0: the
+// band's first MB row; a top edge whose upper MB lies above it is left unfiltered and flagged.
+DEV void edge_flags(const MPic& P, int r, DbLds& D, int h, int row0, int* err)
 {
     const h264r_mb q = P.mbs[r];
     const int idc = P.sl[q.slice].deblock_idc;
@@ -891,6 +899,10 @@ DEV void edge_flags(const MPic& P, int r, DbLds& D, int h)
     bool fl = false, ft = false;
     if (idc == 0) { fl = Ln >= 0; ft = Un >= 0; }
     else if (idc == 2) { fl = Ln >= 0 && P.mbs[Ln].slice == q.slice; ft = Un >= 0 && P.mbs[Un].slice == q.slice; }
+    if (ft && Un / P.wmb < row0) {                                         // the band's contract (above)
+        __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ft = false;
+    }
     for (int c = 0; c < 2; ++c) {
         D.fv[h][c][0] = fl; D.fh[h][c][0] = ft;
         for (int e = 1; e < 4; ++e) D.fv[h][c][e] = D.fh[h][c][e] = 1;
@@ -992,13 +1004,14 @@ DEV void filter_pel(const MPic& P, DbLds& D, int r, int h, bool chroma, int pl, 
 using namespace h264r;
 
 // ------------------------------------------------------------------ kernels
-// I_PCM and inter MBs, one 256-thread workgroup per MB: thread t is luma sample (t % 16, t / 16)
-// and, for t < 128, chroma sample (t % 8, (t / 8) % 8) of plane 1 + t / 64.
-extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, int* err)
+// I_PCM and inter MBs, one 256-thread workgroup per MB of the band: thread t is luma sample
+// (t % 16, t / 16) and, for t < 128, chroma sample (t % 8, (t / 8) % 8) of plane 1 + t / 64.
+extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, int2 rows, int* err)
 {
     __shared__ ResLds R;
     __shared__ int pr[3][256];                                             // an SP MB's prediction
-    const int nmb = b.width_mbs * b.height_mbs, pic = blockIdx.x / nmb, r = blockIdx.x % nmb, t = threadIdx.x;
+    const int nmb = b.width_mbs * (rows.y - rows.x), pic = blockIdx.x / nmb, t = threadIdx.x;
+    const int r = rows.x * b.width_mbs + blockIdx.x % nmb;
     const MPic P = mpic(b, pic);
     const h264r_mb m = P.mbs[r];
     const h264r_slice& sl = P.sl[m.slice];
@@ -1055,11 +1068,12 @@ extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, i
     }
 }
 
-// Intra MBs of the pairs on anti-diagonal `diag` (x + 2 y), one 256-thread workgroup per pair.
-extern "C" __global__ __launch_bounds__(256) void k_mbaff_intra(h264r_batch b, int diag, int* err)
+// Intra MBs of the band's pairs on anti-diagonal `diag` (x + 2 y), one 256-thread workgroup per pair.
+extern "C" __global__ __launch_bounds__(256) void k_mbaff_intra(h264r_batch b, int diag, int2 rows, int* err)
 {
     __shared__ IntraLds L;
-    const int HP = b.height_mbs / 2, pic = blockIdx.x / HP, py = blockIdx.x % HP, px = diag - 2 * py, t = threadIdx.x;
+    const int HP = (rows.y - rows.x) / 2, pic = blockIdx.x / HP, py = rows.x / 2 + blockIdx.x % HP;
+    const int px = diag - 2 * py, t = threadIdx.x;
     if (px < 0 || px >= b.width_mbs) return;
     const MPic P = mpic(b, pic);
     const int rt = (2 * py) * P.wmb + px, rb = rt + P.wmb;
@@ -1132,18 +1146,21 @@ extern "C" __global__ __launch_bounds__(256) void k_mbaff_intra(h264r_batch b, i
     (void)err;
 }
 
-// The loop filter of the pairs on anti-diagonal `diag`, one wave per pair: the strengths of both
-// MBs, then each MB's vertical and horizontal edges in the reference's order (deblock.cc:488-552);
+// The loop filter of the band's pairs on anti-diagonal `diag`, one wave per pair: the strengths of
+// both MBs, then each MB's vertical and horizontal edges in the reference's order (deblock.cc:488-552);
 // lanes 0..15 the luma lines of an edge, 16..23 Cb, 24..31 Cr.
-extern "C" __global__ __launch_bounds__(64) void k_mbaff_deblock(h264r_batch b, int diag, int* err)
+extern "C" __global__ __launch_bounds__(64) void k_mbaff_deblock(h264r_batch b, int diag, int2 rows, int* err)
 {
     __shared__ DbLds D;
-    const int HP = b.height_mbs / 2, pic = blockIdx.x / HP, py = blockIdx.x % HP, px = diag - 2 * py, t = threadIdx.x;
+    const int HP = (rows.y - rows.x) / 2, pic = blockIdx.x / HP, py = rows.x / 2 + blockIdx.x % HP;
+    const int px = diag - 2 * py, t = threadIdx.x;
     if (px < 0 || px >= b.width_mbs) return;
     const MPic P = mpic(b, pic);
     const int r0 = (2 * py) * P.wmb + px;
     const int Wl = P.wmb * 16, Hl = P.hmb * 16, Wc = P.wmb * 8, Hc = P.hmb * 8;
-    if (t < 2) edge_flags(P, r0 + t * P.wmb, D, t);
+    // the rows above the band's first pair row are another rank's: never filtered (edge_flags), never stored
+    const int ymin = (2 * py == rows.x && rows.x > 0) ? 0 : -8;
+    if (t < 2) edge_flags(P, r0 + t * P.wmb, D, t, rows.x, err);
     for (int k = t; k < DYH * DYW; k += 64) {
         const int gx = px * 16 + k % DYW - 4, gy = py * 32 + k / DYW - 8;
         D.ty[k] = (gx >= 0 && gx < Wl && gy >= 0 && gy < Hl) ? P.out[0][(size_t)gy * Wl + gx] : 0;
@@ -1193,14 +1210,13 @@ extern "C" __global__ __launch_bounds__(64) void k_mbaff_deblock(h264r_batch b, 
     }
     for (int k = t; k < DYH * DYW; k += 64) {
         const int x = k % DYW - 4, y = k / DYW - 8, gx = px * 16 + x, gy = py * 32 + y;
-        if ((x < 0 && y < 0) || gx < 0 || gy < 0 || gy >= Hl) continue;
+        if ((x < 0 && y < 0) || y < ymin || gx < 0 || gy < 0 || gy >= Hl) continue;
         P.out[0][(size_t)gy * Wl + gx] = D.ty[k];
     }
     for (int k = t; k < 2 * DCH * DCW; k += 64) {
         const int pl2 = k / (DCH * DCW), e = k % (DCH * DCW), x = e % DCW - 4, y = e / DCW - 8;
         const int gx = px * 8 + x, gy = py * 16 + y;
-        if ((x < 0 && y < 0) || gx < 0 || gy < 0 || gy >= Hc) continue;
+        if ((x < 0 && y < 0) || y < ymin || gx < 0 || gy < 0 || gy >= Hc) continue;
         P.out[1 + pl2][(size_t)gy * Wc + gx] = D.tc[pl2][e];
     }
-    (void)err;
 }

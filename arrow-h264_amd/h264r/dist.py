@@ -127,19 +127,46 @@ def min_over_ranks(value: float, device=None) -> float:
 # output sets per group, alternating), and the exchange only has to bring in the rows of the
 # other ranks' bands that this rank's motion compensation can reach.
 
-ROW_BYTES_PER_MB_COL = (256, 64, 64)       # bytes of one MB row per MB column: Y, Cb, Cr
+ROW_BYTES_PER_MB_COL = (256, 64, 64)       # bytes of one MB row per MB column: Y, Cb, Cr (4:2:0)
 
 
-def halo_mb_rows(max_abs_mvy_qpel: int) -> int:
+def row_bytes_per_mb_col(chroma_format: int = 1) -> tuple[int, int, int]:
+    """Bytes of one MB row per MB column (Y, Cb, Cr) for chroma_format_idc 0..3: a chroma MB is
+    absent (4:0:0), 8 x 8 (4:2:0), 8 x 16 (4:2:2) or 16 x 16 (4:4:4) -- include/h264r_group.h."""
+    if chroma_format not in (0, 1, 2, 3):
+        raise ValueError(f"chroma_format {chroma_format}")
+    c = (0, 64, 128, 256)[chroma_format]
+    return (256, c, c)
+
+
+def halo_mb_rows(max_abs_mvy_qpel: int, mbaff: bool = False) -> int:
     """MB rows of a reference picture above / below a band that the band's motion
     compensation can read, for vertical motion vectors |mv_y| <= max_abs_mvy_qpel.
     Luma (get_block_luma, inter_prediction.cc:158-340): a 4x4 block at rows Y..Y+3 reads
     rows y-2 .. y+6 with y = Y + floor(mv_y / 4): ceil(m / 4) + 2 rows above the band,
     floor(m / 4) + 3 below.  Chroma (get_block_chroma :342-406, 4:2:0): rows yc .. yc+2 with
     yc = Yc + floor(mv_y / 8): at most ceil(m / 8) + 1 chroma rows = ceil(m / 4) + 2 luma rows.
-    Rows past the picture edge are clamped (:185-186), i.e. read inside the picture."""
+    Rows past the picture edge are clamped (:185-186), i.e. read inside the picture.
+    The other chroma formats need the same: 4:2:2 and 4:4:4 chroma rows are luma rows, with the
+    chroma vector mv_y (quarter samples of those rows) and a 2-tap window inside the luma one.
+
+    mbaff=True: the picture is an MBAFF frame and a field MB may carry that vector.  A field MB
+    of pair row p predicts from one FIELD of the reference (get_ref_pic dpb.cc:1046-1055), its
+    block rows counted in field rows (block_y_aff, inter_prediction.cc:470-474): the band's
+    frame rows [16 r0, 16 r1) (r0, r1 even) are field rows [8 r0, 8 r1) of either parity, and
+    field row f of parity b is frame row 2 f + b.  Luma: the window above is ceil(m / 4) + 2
+    field rows, below floor(m / 4) + 3, so at most 2 (ceil(m / 4) + 3) frame rows either way
+    -- twice the frame MB's reach.  Chroma (4:2:0): a field of the opposite parity shifts the
+    vector by -2 or +2 quarter luma samples (:356-361), so |mv_y| <= m + 2; the window reaches
+    at most floor((m + 2) / 8) + 1 chroma field rows = 2 (floor((m + 2) / 8) + 1) chroma frame
+    rows = 4 (floor((m + 2) / 8) + 1) luma rows.  The frame MBs of such a picture reach what
+    the frame formula gives, which is less."""
     m = max(0, int(max_abs_mvy_qpel))
-    return -(-((m + 3) // 4 + 3) // 16)
+    if not mbaff:
+        return -(-((m + 3) // 4 + 3) // 16)
+    luma = 2 * ((m + 3) // 4 + 3)
+    chroma = 4 * ((m + 2) // 8 + 1)
+    return -(-max(luma, chroma) // 16)
 
 
 def halo_plan(bands, rank: int, halo: int):
@@ -177,16 +204,21 @@ class BandExchange:
     RCCL ncclSend / ncclRecv on the decode stream, unpack kernel; over gloo the library's callback
     transport with torch.distributed operations on host buffers).  impl "torch" is the same
     exchange in torch.distributed calls (round 4), kept for comparison.  With gloo (CPU
-    rehearsal) device tensors are staged through host memory."""
+    rehearsal) device tensors are staged through host memory.
+
+    chroma_format (chroma_format_idc 0..3) fixes the planes' row sizes (row_bytes_per_mb_col) under
+    both impls; a 4:0:0 exchange takes two chroma planes of no rows.  MBAFF frames need nothing of
+    their own here: their planes are frame planes and their bands even MB rows."""
 
     def __init__(self, bands, rank: int, width_mbs: int, height_mbs: int, nk: int, mode: str, halo: int,
-                 device, group=None, impl: str = "abi"):
+                 device, group=None, impl: str = "abi", chroma_format: int = 1):
         import torch
         import torch.distributed as dist
         self.bands, self.rank, self.nk, self.mode, self.group = list(bands), rank, nk, mode, group
         self.impl = impl
         self.W, self.H = width_mbs, height_mbs
-        self.rb = [c * width_mbs for c in ROW_BYTES_PER_MB_COL]           # bytes per MB row, per plane
+        self.chroma_format = chroma_format
+        self.rb = [c * width_mbs for c in row_bytes_per_mb_col(chroma_format)]   # bytes per MB row, per plane
         self.mbrow = sum(self.rb)
         self.psz = [r * height_mbs for r in self.rb]                      # plane bytes
         self.world = len(self.bands)
@@ -208,7 +240,7 @@ class BandExchange:
             gloo = dist.get_backend(group) == "gloo"
             self.grp = Group(self.world, rank, dev.index if dev.type == "cuda" else -1,
                              "torch" if gloo else "rccl", group)
-            self.grp.set_bands(width_mbs, height_mbs, self.bands, mode, halo, nk)
+            self.grp.set_bands(width_mbs, height_mbs, self.bands, mode, halo, nk, chroma_format)
             return
         if impl != "torch":
             raise ValueError(impl)
@@ -255,8 +287,9 @@ class BandExchange:
         if self.impl == "abi":
             import torch
             stream = torch.cuda.current_stream(planes[0].device).cuda_stream if planes[0].is_cuda else None
-            self.grp.exchange(self.nk, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
-                              self.psz[0], self.psz[1], stream)
+            # 4:0:0: two planes of no rows (the library takes NULL chroma on such a group)
+            u, v = (planes[1].data_ptr(), planes[2].data_ptr()) if self.rb[1] else (None, None)
+            self.grp.exchange(self.nk, planes[0].data_ptr(), u, v, self.psz[0], self.psz[1], stream)
             return
         views = self._views(planes)
         gloo = dist.get_backend(self.group) == "gloo" and self.device != "cpu" and str(self.device) != "cpu"

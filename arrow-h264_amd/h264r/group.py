@@ -36,6 +36,7 @@ def bind(L) -> None:
         "h264r_group_destroy": ([P], I),
         "h264r_group_plan": ([I, I, P, I, I, P, P], I),
         "h264r_group_set_bands": ([P, I, I, P, I, I, I], I),
+        "h264r_group_set_bands_fmt": ([P, I, I, I, P, I, I, I], I),
         "h264r_group_exchange": ([P, I, P, P, P, I64, I64, P], I),
         "h264r_group_stats": ([P, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)], I),
     }
@@ -141,13 +142,17 @@ class Group:
             raise ValueError(transport)
         self.nranks, self.rank, self.device, self.transport = nranks, rank, device, transport
 
-    def set_bands(self, width_mbs: int, height_mbs: int, bands, mode: str, halo: int, max_pics: int) -> None:
+    def set_bands(self, width_mbs: int, height_mbs: int, bands, mode: str, halo: int, max_pics: int,
+                  chroma_format: int = 1) -> None:
+        """h264r_group_set_bands_fmt: chroma_format (chroma_format_idc 0..3) fixes the planes' row sizes."""
         b = _bands_array(bands)
-        _check("h264r_group_set_bands", self._L.h264r_group_set_bands(self._h, width_mbs, height_mbs, b.ctypes.data,
-                                                                       MODES[mode], halo, max_pics))
+        _check("h264r_group_set_bands_fmt",
+               self._L.h264r_group_set_bands_fmt(self._h, width_mbs, height_mbs, chroma_format, b.ctypes.data,
+                                                 MODES[mode], halo, max_pics))
 
     def exchange(self, num_pics: int, y: int, u: int, v: int, stride_y: int, stride_c: int, stream=None) -> None:
-        """y / u / v: addresses of picture 0's planes (device or host); stream: a hipStream_t address."""
+        """y / u / v: addresses of picture 0's planes (device or host; u = v = None on a 4:0:0 group);
+        stream: a hipStream_t address."""
         _check("h264r_group_exchange", self._L.h264r_group_exchange(self._h, num_pics, y, u, v, stride_y, stride_c,
                                                                      stream))
 

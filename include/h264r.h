@@ -407,7 +407,12 @@ int  h264r_decode_batch(h264r_ctx* ctx, const h264r_batch* batch, void* stream);
  * then independent of the rows outside it.  Motion compensation still reads whole
  * reference pictures.  A band whose top edge would be filtered is reported by
  * h264r_check() as H264R_EDEVICE.  Replaces nothing in the reference (its decoder is
- * single-threaded); the slice walk it parallelises is slice_data.cc:640-650. */
+ * single-threaded); the slice walk it parallelises is slice_data.cc:640-650.
+ * MBAFF frames (batch.mbaff): bands are made of MB pairs, so row0 and row1 must be even
+ * (H264R_EINVAL otherwise); the same contract holds for the pairs of the band's first pair row,
+ * whose top edges -- a field pair's two, a frame pair's one -- are neither filtered nor the rows
+ * above them written, and the same report when one of them would be filtered.  Implicit weights
+ * from field POCs, lossless MBs and SP slices decode in a band as in a whole picture. */
 int  h264r_decode_batch_rows(h264r_ctx* ctx, const h264r_batch* batch, int row0, int row1, void* stream);
 /* Device pointer of DPB slot planes (for building h264r_batch.ref_planes). */
 int  h264r_ref_planes(h264r_ctx* ctx, int slot, uint8_t** y, uint8_t** u, uint8_t** v);

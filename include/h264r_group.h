@@ -17,8 +17,12 @@
  * and never touches a GPU).
  *
  * Layout: plane k of picture i starts at base[k] + i * stride[k] bytes (the h264r_batch out
- * planes: stride 256 * W * H for luma, 64 * W * H for chroma); rows are full width.  A peer's
- * segment of the staging buffers holds, per picture, its luma rows then its Cb then its Cr rows.
+ * planes); rows are full width.  One MB row of the luma plane is 256 * W bytes; one MB row of
+ * each chroma plane is 0, 64 * W, 128 * W or 256 * W bytes for chroma_format_idc 0 (4:0:0, no
+ * chroma planes), 1 (4:2:0), 2 (4:2:2) or 3 (4:4:4), so the strides are at least 256 * W * H and
+ * that chroma row size times H.  A peer's segment of the staging buffers holds, per picture, its
+ * luma rows then its Cb then its Cr rows.  The planes of an MBAFF frame are frame planes and its
+ * bands are even MB rows (h264r_decode_batch_rows): nothing here differs for them.
  */
 #ifndef H264R_GROUP_H_
 #define H264R_GROUP_H_
@@ -74,13 +78,21 @@ int h264r_group_plan(int nranks, int rank, const int32_t* bands, int mode, int h
  * allocates its staging buffers.  May be called again (a new plan). */
 int h264r_group_set_bands(h264r_group* g, int width_mbs, int height_mbs, const int32_t* bands,
                           int mode, int halo_mb_rows, int max_pics);
+/* The same for planes of chroma_format_idc 0..3 (anything else: H264R_EINVAL), which fixes the
+ * bytes of one MB row (Layout above) and with them every staging size and transfer size.
+ * h264r_group_set_bands is the chroma_format_idc = 1 case.  Additive: no struct changes, and
+ * H264R_ABI_VERSION stays what it is, as for the other entry points of this header. */
+int h264r_group_set_bands_fmt(h264r_group* g, int width_mbs, int height_mbs, int chroma_format_idc,
+                              const int32_t* bands, int mode, int halo_mb_rows, int max_pics);
 
 /* After this rank has decoded its band of num_pics pictures into the planes, bring in the rows
  * of the other bands the plan names, in place.  RCCL: enqueued on `stream` (a hipStream_t,
  * NULL = the legacy stream) and asynchronous, like h264r_decode_batch -- a decode of the next
  * pictures on the same stream reads the received rows.  Callback transport: returns when the
  * rows are in place.  A group's staging buffers are reused by every exchange: drive a group from
- * one stream (or order the streams), as a context. */
+ * one stream (or order the streams), as a context.  stride_y / stride_c are checked against the
+ * group's format; a 4:0:0 group moves luma only, takes u == v == NULL and ignores stride_c (NULL
+ * chroma on any other format is H264R_EINVAL). */
 int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, uint8_t* v,
                          int64_t stride_y, int64_t stride_c, void* stream);
 
