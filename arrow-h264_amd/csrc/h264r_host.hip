@@ -22,7 +22,9 @@
 #include <vector>
 
 #include "h264r.h"
+#include "h264r_output.h"
 #include "launch_cfg.h"
+#include "output_job.h"
 #include "wp_math.h"
 
 #ifndef H264R_WALK_ROWS
@@ -62,6 +64,7 @@ extern "C" __global__ void k_deblock2y(h264r_batch b, const h264r::DbInfo* dbinf
                                       int* sync, int* err, uint32_t epoch, int2 rows, int nx, const uint8_t* recon);
 extern "C" __global__ void k_deblock2c(h264r_batch b, const h264r::DbInfo* dbinfo, uint64_t* hb,
                                       int* sync, int* err, uint32_t epoch, int2 rows, int nx, const uint8_t* recon);
+extern "C" __global__ void k_output(h264r::OutJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
 constexpr size_t DBINFO_BYTES = 80;
 constexpr size_t HANDOFF_BYTES = 256;   // one tagged record (32 x {dword, epoch}) per MB
 constexpr size_t HANDOFF2_BYTES = 384;  // k_deblock2: 2 row slots x 24 x {dword, tag} per MB column
@@ -1089,6 +1092,102 @@ int h264r_last_timing(h264r_ctx* c, float out[4])
     c->spans.clear();
     c->ev_used = 0;
     c->timed_launches = 0;
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- output stage (h264r_output.h)
+// The planes of one output frame: the geometry (output.cc:135-165) and the layout, as the job k_output
+// takes and, for the caller, as an h264r_out_geom.
+static int output_plan(int fmt, const h264r_out_desc* d, h264r_out_geom* g, h264r::OutJob* job)
+{
+    if (!d || fmt < 0 || fmt > 3 || d->width_mbs <= 0 || d->frame_height_mbs <= 0 ||
+        d->width_mbs > H264R_OUT_MAX_MBS || d->frame_height_mbs > H264R_OUT_MAX_MBS ||
+        (d->frame_mbs_only != 0 && d->frame_mbs_only != 1) ||
+        (d->layout != H264R_OUT_PLANAR && d->layout != H264R_OUT_SEMIPLANAR))
+        return H264R_EINVAL;
+    const int pa = d->pitch_align;
+    if (pa < 0 || pa > H264R_OUT_MAX_PITCH_ALIGN || (pa & (pa - 1))) return H264R_EINVAL;
+    if (d->crop_left < 0 || d->crop_right < 0 || d->crop_top < 0 || d->crop_bottom < 0) return H264R_EINVAL;
+    if (d->fake_chroma && fmt != 0) return H264R_EUNSUPPORTED;
+    const int sub_w = (fmt == 1 || fmt == 2) ? 2 : 1, sub_h = fmt == 1 ? 2 : 1;    // 4:0:0: CropUnitX 1
+    const int mb_cw = fmt ? 16 / sub_w : 0, mb_ch = fmt ? 16 / sub_h : 0;
+    const int64_t uy = 2 - d->frame_mbs_only;
+    const int64_t lc = d->crop_left, rc = d->crop_right, tc = d->crop_top * uy, bc = d->crop_bottom * uy;
+    const int64_t lw = 16 * (int64_t)d->width_mbs - sub_w * (lc + rc);
+    const int64_t lh = 16 * (int64_t)d->frame_height_mbs - sub_h * (tc + bc);
+    const int64_t cw = fmt ? mb_cw * (int64_t)d->width_mbs - (lc + rc) : 0;
+    const int64_t ch = fmt ? mb_ch * (int64_t)d->frame_height_mbs - (tc + bc) : 0;
+    if (lw <= 0 || lh <= 0 || (fmt && (cw <= 0 || ch <= 0))) return H264R_EINVAL;
+
+    h264r::OutJob J{};
+    auto plane = [&](int mode, int64_t w, int64_t h, int64_t x0, int64_t y0, int src_pitch) {
+        h264r::OutPlane& p = J.pl[J.nplanes];
+        p.off = J.nplanes ? J.pl[J.nplanes - 1].off + J.pl[J.nplanes - 1].pitch * J.pl[J.nplanes - 1].h : 0;
+        p.pitch = pa > 1 ? (w + pa - 1) / pa * pa : w;
+        p.w = (int32_t)w; p.h = (int32_t)h; p.x0 = (int32_t)x0; p.y0 = (int32_t)y0;
+        p.src_pitch = src_pitch; p.mode = mode;
+        ++J.nplanes;
+    };
+    plane(h264r::OUT_COPY_Y, lw, lh, sub_w * lc, sub_h * tc, 16 * d->width_mbs);
+    const bool semi = d->layout == H264R_OUT_SEMIPLANAR;
+    if (fmt) {
+        const int cp = mb_cw * d->width_mbs;
+        if (semi) plane(h264r::OUT_INTERLEAVE, 2 * cw, ch, lc, tc, cp);
+        else { plane(h264r::OUT_COPY_U, cw, ch, lc, tc, cp); plane(h264r::OUT_COPY_V, cw, ch, lc, tc, cp); }
+    } else if (d->fake_chroma) {
+        const int64_t fu = lw * lh / 4;                          // WriteUV (output.cc:205-224): one run per plane
+        if (fu > 0) {
+            if (semi) plane(h264r::OUT_FILL, 2 * fu, 1, 0, 0, 0);
+            else { plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); }
+        }
+    }
+    J.need_chroma = fmt != 0;
+    const h264r::OutPlane& last = J.pl[J.nplanes - 1];
+    const int64_t frame_bytes = last.off + last.pitch * last.h;
+    if (g) {
+        *g = h264r_out_geom{};
+        const int32_t l[4] = {(int32_t)(sub_w * lc), (int32_t)(sub_h * tc), (int32_t)lw, (int32_t)lh};
+        const int32_t cr[4] = {(int32_t)lc, (int32_t)tc, (int32_t)cw, (int32_t)ch};
+        for (int k = 0; k < 4; ++k) { g->luma[k] = l[k]; g->chroma[k] = fmt ? cr[k] : 0; }
+        for (int k = 0; k < J.nplanes; ++k) { g->plane_off[k] = J.pl[k].off; g->plane_pitch[k] = J.pl[k].pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) { *job = J; job->frame_stride = frame_bytes; }
+    return H264R_OK;
+}
+
+int h264r_output_geometry(int chroma_format_idc, const h264r_out_desc* desc, h264r_out_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return output_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_out_frame* frames, int num_frames,
+                        uint8_t* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::OutJob job;
+    const int st = output_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.frame_stride = dst_frame_stride;
+    job.num_frames = num_frames;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    // the sources are, as a rule, what the context's last launch wrote: ordered as run_batch orders launches
+    if (c->last_stream && c->last_stream != s) {
+        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
+        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
+    }
+    c->last_stream = s;
+    int items = 0;
+    for (int k = 0; k < job.nplanes; ++k)
+        items = std::max(items, job.pl[k].h * h264r::out_chunks_per_row(job.pl[k].w));
+    const int per = h264r::OUT_THREADS * h264r::OUT_ITEMS;
+    const dim3 grid((unsigned)((items + per - 1) / per), (unsigned)std::min(num_frames, 65535), (unsigned)job.nplanes);
+    hipLaunchKernelGGL(k_output, grid, dim3(h264r::OUT_THREADS), 0, s, job, frames, dst, c->d_err);
+    HIP_OK(hipGetLastError());
     return H264R_OK;
 }
 

@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
     A.bind_synth(L)
     from .group import bind as bind_group
     bind_group(L)
+    from .output import bind as bind_output
+    bind_output(L)
     if L.h264r_abi_version() != A.ABI_VERSION:
         raise ImportError("libh264r ABI version mismatch")
     _lib = L

@@ -13,6 +13,7 @@ Host-side byte shuffling only (strided row copies); nothing here computes sample
 """
 from __future__ import annotations
 
+import ctypes as C
 import hashlib
 import io
 import os
@@ -184,3 +185,166 @@ def compare_yuv(source: str | os.PathLike | bytes, digest_file: str | os.PathLik
     """The harness's compare() for a decoded file against its `*.yuv.md5`."""
     hashes = read_digests(digest_file)
     return compare(digest_by_frames(source, len(hashes)), hashes, name)
+
+
+# --------------------------------------------------------------------------------------------
+# The device-side output stage (include/h264r_output.h): the same frames -- cropped, field pairs
+# woven, 4:0:0 with the reference's 128 chroma, planar or semi-planar -- written by the GPU from
+# planes that are already there.  ctypes mirror of the header, and DeviceOutput over torch tensors.
+PLANAR, SEMIPLANAR = 0, 1                                         # h264r_out_desc.layout
+OUT_FRAME, OUT_FIELD_PAIR, OUT_UNPAIRED_TOP, OUT_UNPAIRED_BOT = 0, 1, 2, 3   # h264r_out_frame.kind
+
+
+class OutDesc(C.Structure):
+    """h264r_out_desc"""
+    _fields_ = [("width_mbs", C.c_int32), ("frame_height_mbs", C.c_int32),
+                ("crop_left", C.c_int32), ("crop_right", C.c_int32), ("crop_top", C.c_int32),
+                ("crop_bottom", C.c_int32), ("frame_mbs_only", C.c_int32), ("layout", C.c_int32),
+                ("pitch_align", C.c_int32), ("fake_chroma", C.c_int32)]
+
+
+class OutGeom(C.Structure):
+    """h264r_out_geom"""
+    _fields_ = [("luma", C.c_int32 * 4), ("chroma", C.c_int32 * 4), ("plane_off", C.c_int64 * 3),
+                ("plane_pitch", C.c_int64 * 3), ("frame_bytes", C.c_int64)]
+
+
+# h264r_out_frame: kind, pad, y[2], u[2], v[2]
+OUT_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("pad", "<i4"), ("y", "<u8", (2,)), ("u", "<u8", (2,)), ("v", "<u8", (2,))])
+assert OUT_FRAME_DTYPE.itemsize == 56
+
+
+def bind(L) -> None:
+    """Declare the prototypes of include/h264r_output.h on the library (h264r.lib())."""
+    P, I = C.c_void_p, C.c_int
+    L.h264r_output_geometry.argtypes = [I, C.POINTER(OutDesc), C.POINTER(OutGeom)]
+    L.h264r_output_geometry.restype = I
+    L.h264r_output_frames.argtypes = [P, C.POINTER(OutDesc), P, I, P, C.c_int64, P]
+    L.h264r_output_frames.restype = I
+
+
+@dataclass(frozen=True)
+class DeviceGeometry:
+    """h264r_out_geom: the crop windows inside the coded planes and the layout of one output frame."""
+    luma: tuple[int, int, int, int]
+    chroma: tuple[int, int, int, int]
+    plane_off: tuple[int, int, int]
+    plane_pitch: tuple[int, int, int]
+    frame_bytes: int
+
+
+def _desc(width_mbs: int, frame_height_mbs: int, crop: Crop, layout: int, pitch_align: int, fake_chroma) -> OutDesc:
+    return OutDesc(width_mbs, frame_height_mbs, crop.left, crop.right, crop.top, crop.bottom, crop.frame_mbs_only,
+                   layout, pitch_align, int(fake_chroma))
+
+
+def device_geometry(width_mbs: int, frame_height_mbs: int, crop: Crop = Crop(), chroma_format: int = 1,
+                    layout: int = PLANAR, pitch_align: int = 0, fake_chroma: bool = False) -> DeviceGeometry:
+    """h264r_output_geometry (host only, no GPU): raises H264RError with the library's status."""
+    from . import _check, lib
+    g = OutGeom()
+    d = _desc(width_mbs, frame_height_mbs, crop, layout, pitch_align, fake_chroma)
+    _check("h264r_output_geometry", lib().h264r_output_geometry(chroma_format, C.byref(d), C.byref(g)))
+    return DeviceGeometry(tuple(g.luma), tuple(g.chroma), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+
+
+def pair_fields(structures: Sequence[int], pocs: Sequence[int]) -> list[tuple[int, int, int]]:
+    """Decoded pictures (decoding order: h264r_pic.structure and POC of each) -> the output frames, in
+    output order, as (kind, picture, second picture or -1).  Two consecutive field pictures of opposite
+    parity make one H264R_OUT_FIELD_PAIR (top field first in the tuple, whichever was decoded first)
+    with the smaller of their POCs; a field without its partner is an unpaired field; frames and MBAFF
+    frames are H264R_OUT_FRAME.  Frames leave in POC order inside each IDR period, a new period at
+    every POC 0 after the first frame -- the order the reference's DPB writes them (dpb.cc)."""
+    TOP, BOTTOM = 1, 2                                   # H264R_TOP_FIELD, H264R_BOTTOM_FIELD
+    frames, i, n = [], 0, len(structures)
+    while i < n:
+        st, poc = int(structures[i]), int(pocs[i])
+        if st not in (TOP, BOTTOM):
+            frames.append((poc, OUT_FRAME, i, -1))
+            i += 1
+        elif i + 1 < n and int(structures[i + 1]) == TOP + BOTTOM - st:
+            top, bot = (i, i + 1) if st == TOP else (i + 1, i)
+            frames.append((min(poc, int(pocs[i + 1])), OUT_FIELD_PAIR, top, bot))
+            i += 2
+        else:
+            frames.append((poc, OUT_UNPAIRED_TOP if st == TOP else OUT_UNPAIRED_BOT, i, -1))
+            i += 1
+    keys, period = [], 0
+    for k, f in enumerate(frames):
+        if k and f[0] == 0:
+            period += 1
+        keys.append((period, f[0], k))
+    return [frames[k][1:] for _, _, k in sorted(keys)]
+
+
+@dataclass
+class FrameTable:
+    """A device array of h264r_out_frame and what keeps its sources alive."""
+    tensor: object                  # torch uint8 [n * 56] on the device
+    n: int
+    keep: list
+
+
+class DeviceOutput:
+    """h264r_output_frames for one geometry on one Decoder (its chroma format and device).
+
+        out = DeviceOutput(dec, W, H, Crop(bottom=4))
+        table = out.frames_from([(OUT_FRAME, (y, u, v)), (OUT_FIELD_PAIR, (ty, tu, tv), (by, bu, bv))])
+        frames = out.run(table)             # torch uint8 [n, frame_bytes] on the device
+    """
+
+    def __init__(self, decoder, width_mbs: int, frame_height_mbs: int, crop: Crop = Crop(), layout: int = PLANAR,
+                 pitch_align: int = 0, fake_chroma: bool = False):
+        self.decoder = decoder
+        self.chroma_format = decoder._fmt
+        self.desc = _desc(width_mbs, frame_height_mbs, crop, layout, pitch_align, fake_chroma)
+        self.geom = device_geometry(width_mbs, frame_height_mbs, crop, self.chroma_format, layout, pitch_align,
+                                    fake_chroma)
+
+    @staticmethod
+    def _addr(x) -> int:
+        if x is None:
+            return 0
+        return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+    def frames_from(self, kinds_and_tensors, device: str = "cuda") -> FrameTable:
+        """The device frame table of [(kind, (y, u, v)[, (y, u, v) of the bottom field])]: planes are
+        torch tensors on the device or raw device addresses; None is a NULL pointer (u, v on 4:0:0)."""
+        import torch
+        rows = list(kinds_and_tensors)
+        tab = np.zeros(len(rows), OUT_FRAME_DTYPE)
+        keep = []
+        for i, row in enumerate(rows):
+            tab[i]["kind"] = int(row[0])
+            for s, planes in enumerate(row[1:3]):
+                if planes is None:
+                    continue
+                for name, p in zip(("y", "u", "v"), planes):
+                    tab[i][name][s] = self._addr(p)
+                    keep.append(p)
+        t = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).to(device)
+        return FrameTable(t, len(rows), keep)
+
+    def run(self, table, n: int | None = None, dst=None, stream: int | None = None):
+        """Write n frames (default: the whole table).  dst: a torch uint8 tensor [n, dst_frame_stride]
+        on the device (written in place: padding and the bytes past frame_bytes keep what they hold) or
+        None = a new [n, frame_bytes] tensor.  Asynchronous on `stream` (a hipStream_t address; None =
+        the context's stream): Decoder.check() before the result is read on another stream."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("run: n is needed with a raw frame table")
+        if dst is None:
+            dst = torch.empty((n, self.geom.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("run: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
+        stride = dst.stride(0)
+        L = self.decoder._L
+        _check("h264r_output_frames", L.h264r_output_frames(self.decoder.handle, C.byref(self.desc), C.c_void_p(tptr), n,
+                                                           C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
+        return dst
