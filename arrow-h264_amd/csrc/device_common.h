@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "h264r.h"
+#include "kernels.h"
 
 #define DEV __device__ __forceinline__
 
@@ -72,7 +73,7 @@ DEV void wave_sync()
 // stream, XCC ids that are not contiguous modulo nx) would leave its pictures unfiltered.
 // Every wave passes here once, when its XCD's tickets have run out; the last one checks
 // that every XCD's tickets were all taken (a counter that was reached ends past its item
-// count) and flags err[0] = 3 otherwise -- a failure is never silent.  One-wave workgroups.
+// count) and flags err[0] = DEV_ERR_SCHEDULE otherwise -- a failure is never silent.  One-wave workgroups.
 template <typename ItemsOf>
 DEV void xcd_drain_check(const int* tickets, int* done, int nx, ItemsOf items_of, int* err)
 {
@@ -81,7 +82,7 @@ DEV void xcd_drain_check(const int* tickets, int* done, int nx, ItemsOf items_of
     if (prev != (int)gridDim.x - 1) return;
     for (int k = 0; k < nx; ++k)
         if (__hip_atomic_load(&tickets[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < items_of(k))
-            __hip_atomic_store(err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(err, DEV_ERR_SCHEDULE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 DEV int mb_is_intra(const h264r_mb& m) { return (m.flags & H264R_MBF_INTRA) != 0; }
@@ -90,7 +91,7 @@ DEV int mb_is_intra(const h264r_mb& m) { return (m.flags & H264R_MBF_INTRA) != 0
 // Every cross-wave wait of the kernels (row hand-offs, the level barrier) is bounded in
 // WALL time, not in polls: err[0] is the context's error word (h264r_check), err[1] the
 // bound in s_memrealtime ticks (100 MHz), written by the host.  A wait gives up when its
-// own bound has passed (it then flags err[0] = 1) or as soon as another wave has flagged
+// own bound has passed (it then flags err[0] = DEV_ERR_WAIT) or as soon as another wave has flagged
 // an error, so one expired wait drains the whole grid within a few polls instead of
 // every waiter behind it serving its own full bound (the round-2 hang: chained
 // poll-count bounds of ~17 s each).  Checked every 64 polls (one scalar clock read).
@@ -107,7 +108,7 @@ DEV bool wait_give_up(int* err, WaitClock& c)
     if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
     const uint32_t lim = (uint32_t)__hip_atomic_load(err + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (now - c.t0 <= (uint64_t)lim) return false;
-    __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(err, DEV_ERR_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;
 }
 

@@ -4,12 +4,15 @@
 //   picture_begin / mb_submit / picture_end   ~ Decoder::init, decode(mb), deblock_filter
 //   decode_batch                              ~ decode + deblock_filter of many pictures at once
 // The reconstruction itself never runs on the CPU: every entry point that
-// produces samples launches k_inter / k_intra / k_deblock and fails with
+// produces samples launches the kernels of kernels.h and fails with
 // H264R_ENODEVICE when no gfx950 device is present.
 //
-// Launch sequence per batch: k_inter (every inter / PCM MB, fully parallel),
-// k_intra_pic (intra MBs, banded workgroups walking the wavefront),
-// k_deblock (deblocking, one wave per pair of MB rows walking the wavefront).
+// Launch sequence per batch (recon_launches and deblock_launch below):
+// k_inter4r + k_inter_sp (the deblocking records, every inter / PCM MB, fully parallel),
+// k_level + k_level_scatter + k_intra_levels (intra MBs by dependency level), k_intra_pic (the
+// deeper intra MBs, banded workgroups walking the wavefront), then k_deblock2, its split walk
+// k_deblock2y + k_deblock2c, or k_deblock (deblocking, waves walking bands of MB rows).  4:4:4,
+// 4:2:2 / 4:0:0 and MBAFF batches: run_444, run_422, run_mbaff.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,53 +26,10 @@
 
 #include "h264r.h"
 #include "h264r_output.h"
-#include "launch_cfg.h"
-#include "output_job.h"
+#include "kernels.h"
 #include "wp_math.h"
 
-#ifndef H264R_WALK_ROWS
-#define H264R_WALK_ROWS 8       // k_intra_pic: MB rows per band = waves per workgroup (k_picture.hip)
-#endif
-
-namespace h264r { struct DbInfo; }
-extern "C" __global__ void k_inter4r(h264r_batch b, h264r::DbInfo* dbinfo, int2 rows, int* sp_flag, uint8_t* recon, int tag,
-                                     int* zero, int nz, int* zero2, int nz2);
-extern "C" __global__ void k_inter_sp(h264r_batch b, int2 rows, const int* sp_flag, uint8_t* recon, int tag);
-extern "C" __global__ void k_derive444(h264r_batch b, int pl, int qpl, h264r_mb* mbs, h264r_slice* slices, h264r_quant* quant,
-                                       const uint8_t** refs, int ntab, int* err);
-extern "C" __global__ void k_untile(h264r_batch b, int2 rows, const uint8_t* recon);
-extern "C" __global__ void k_c422_inter(h264r_batch b, int2 rows, int* err);
-extern "C" __global__ void k_c422_intra(h264r_batch b, int2 rows, int* err);
-extern "C" __global__ void k_c422_db(h264r_batch b, const h264r::DbInfo* dbinfo, int2 rows, int* err);
-extern "C" __global__ void k_mbaff_inter(h264r_batch b, int2 rows, int* err);
-extern "C" __global__ void k_mbaff_intra(h264r_batch b, int diag, int2 rows, int* err);
-extern "C" __global__ void k_mbaff_deblock(h264r_batch b, int diag, int2 rows, int* err);
-extern "C" __global__ void k_intra_pic(h264r_batch b, int* sync, int* err, const uint16_t* lvl, int lmax, int2 rows,
-                                      int gstep, uint8_t* recon, const int* pband);
-extern "C" __global__ void k_level(h264r_batch b, uint16_t* lvl, int* lvsync, int* lcount, int2 rows, int deep_cut,
-                                   int lmax, int* pband);
-extern "C" __global__ void k_level_scatter(h264r_batch b, const uint16_t* lvl, const int* lcount, int* lbase, int* lcursor,
-                                           uint32_t* list, int2 rows);
-extern "C" __global__ void k_intra_levels(h264r_batch b, const int* lcount, const int* lbase, const uint32_t* list,
-                                          int lmax, int* lvsync, int* err, uint8_t* recon, int* bar);
-constexpr int LEVEL_MAX_MBS = 65536;      // k_level's LDS bitmap (k_picture.hip)
-constexpr int LEVEL_LDS = 40960;          // k_level's LDS level bytes: (W + 2) x (rows + 1) (k_picture.hip)
-constexpr int LEVEL_LISTS = 64;           // levels with MB lists (H264R_LEVEL_LISTS, k_picture.hip)
-constexpr int LEVEL_IDS = 2 * (LEVEL_LISTS + 1);   // two lists per level (k_picture.hip LEVEL_IDS)
-extern "C" __global__ void k_deblock(h264r_batch b, const h264r::DbInfo* dbinfo, uint64_t* hb,
-                                     int* sync, int* err, uint32_t epoch, int2 rows, int nx, uint8_t* recon);
-extern "C" __global__ void k_deblock2(h264r_batch b, const h264r::DbInfo* dbinfo, uint64_t* hb,
-                                      int* sync, int* err, uint32_t epoch, int2 rows, int nx, const uint8_t* recon);
-extern "C" __global__ void k_deblock2y(h264r_batch b, const h264r::DbInfo* dbinfo, uint64_t* hb,
-                                      int* sync, int* err, uint32_t epoch, int2 rows, int nx, const uint8_t* recon);
-extern "C" __global__ void k_deblock2c(h264r_batch b, const h264r::DbInfo* dbinfo, uint64_t* hb,
-                                      int* sync, int* err, uint32_t epoch, int2 rows, int nx, const uint8_t* recon);
-extern "C" __global__ void k_output(h264r::OutJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
-constexpr size_t DBINFO_BYTES = 80;
-constexpr size_t HANDOFF_BYTES = 256;   // one tagged record (32 x {dword, epoch}) per MB
-constexpr size_t HANDOFF2_BYTES = 384;  // k_deblock2: 2 row slots x 24 x {dword, tag} per MB column
-constexpr int DEBLOCK2_UNITS = 64 / H264R_DB2_LPU;   // k_deblock2: (picture, MB row) units per wave (mb_deblock.h)
-constexpr int DEBLOCK2_PICS = DEBLOCK2_UNITS / H264R_DB2_BAND;   // pictures per wave
+using namespace h264r;
 
 namespace {
 
@@ -118,11 +78,17 @@ int dev_resize(T** p, size_t* cap, size_t n)
 
 }  // namespace
 
+constexpr int OVERLAP_MAX = 16;     // chunks of the overlapped schedule at most (H264R_OVERLAP)
+
 // Per-batch scratch of one launch sequence.
 struct Scratch {
     uint8_t* d_dbinfo = nullptr; size_t c_dbinfo = 0;
-    int* d_sync = nullptr; size_t c_sync = 0;
+    int* d_sync = nullptr; size_t c_sync = 0;      // a sync region (sync_words.h) per chunk of the overlapped schedule
     int tag = 0;                    // launch-sequence tag (> 0): k_inter4r's SP word
+    // the SP word of each chunk: k_inter4r stores the launch tag there when it met an inter MB of
+    // an SP slice.  Allocated and zeroed once and written by nothing else, so a word only ever
+    // holds tags of earlier launches, whatever their shape
+    int* d_sptag = nullptr;
     uint8_t* d_hb = nullptr; size_t c_hb = 0;
     uint32_t epoch = 0;             // tag of the deblocking hand-off records of the last launch
     uint8_t* d_hb2 = nullptr; size_t c_hb2 = 0;
@@ -133,7 +99,7 @@ struct Scratch {
     uint8_t* d_recon = nullptr; size_t c_recon = 0; // MB-tiled reconstruction, 384 B per (picture, MB)
     void release()
     {
-        void* bufs[] = {d_dbinfo, d_sync, d_hb, d_hb2, d_lvl, d_list, d_lcnt, d_recon};
+        void* bufs[] = {d_dbinfo, d_sync, d_sptag, d_hb, d_hb2, d_lvl, d_list, d_lcnt, d_recon};
         for (void* b : bufs) if (b) (void)hipFree(b);
     }
 };
@@ -344,7 +310,7 @@ static const Knobs& knobs()
         v = 0; n.ok &= env_long("H264R_COOP", 0, 1, &v); n.coop = v != 0;
         v = 0; n.ok &= env_long("H264R_WALK_GSTEP", 0, 1 << 20, &v); n.walk_gstep = (int)v;
         // measured slower than one stage (profiles/r05_b_overlap_ab.txt): off by default
-        v = 1; n.ok &= env_long("H264R_OVERLAP", 0, 16, &v); n.overlap = (int)v;
+        v = 1; n.ok &= env_long("H264R_OVERLAP", 0, OVERLAP_MAX, &v); n.overlap = (int)v;
         v = 0; n.ok &= env_long("H264R_VERBOSE", 0, 1, &v); n.verbose = v != 0;
         return n;
     }();
@@ -538,22 +504,15 @@ static h264r_batch sub_batch(const h264r_batch& b, int p0, int n)
     return r;
 }
 
-// ints of one launch sequence's sync region: [intra ticket + per-(picture, row) progress]
-// [deblock ticket][level barrier, deepest level][2 unused] + the deblocking kernels' per-XCD
-// ticket counters and done count (two sets: the split walk's luma and chroma kernels run
-// together) + k_intra_levels' sharded grid barrier (8 shard counters + top) -- these 1 + P H + 32
-// are zeroed by k_inter4r -- then per picture the walk's bands holding an MB deeper than the
-// level lists (k_level -> k_intra_pic), and last the SP tag word (k_inter4r stores the launch
-// tag when it met an inter MB of an SP slice).
-static size_t sync_ints(int P, int H) { return 1 + (size_t)P * H + 32 + (size_t)P + 1; }
-
 // One launch sequence's share of the scratch (the whole batch, or one chunk of the overlapped
-// schedule): its pictures, their deblocking records and MB-tiled reconstruction, its sync region.
+// schedule): its pictures, their deblocking records and MB-tiled reconstruction, its sync region
+// (laid out by sync_words.h for the stage's own pictures) and its SP word.
 struct Stage {
     h264r_batch b;
-    h264r::DbInfo* dbinfo;
+    DbInfo* dbinfo;
     uint8_t* recon;
     int* sync;
+    int* sp_flag;
 };
 
 // The reconstruction of a stage on stream s: k_inter4r + k_inter_sp (the deblocking records and
@@ -567,32 +526,32 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
     const int nbands = (HB + H264R_WALK_ROWS - 1) / H264R_WALK_ROWS;
     const bool wait_test = (c->debug & H264R_DBG_WAIT_TEST) != 0;
     int* sync = S.sync;
+    const SyncWords SW{P, H};
     uint8_t* recon = S.recon;
     const int groups = (W * HB + 15) / 16;
     // groups per workgroup (launch_cfg.h), 8 XCD bands (k_recon.hip inter4_groups)
     const dim3 igrid(8 * ((groups + 8 * H264R_INTER_GROUPS - 1) / (8 * H264R_INTER_GROUPS)), P);
     {
         Timed t(c, 0, s);
-        int* sp_flag = sync + 1 + (size_t)P * H + 32 + P;    // not zeroed: compared with the tag
         // the deblocking records and the inter / I_PCM reconstruction in one launch, which also
         // zeroes the stage's sync words and the level counters
         if (++X.tag <= 0) X.tag = 1;
-        hipLaunchKernelGGL(k_inter4r, igrid, dim3(256), 0, s, b, S.dbinfo, rows, sp_flag, recon, X.tag, sync,
-                           (int)(1 + (size_t)P * H + 32), levels ? X.d_lcnt : nullptr, levels ? 3 * LEVEL_IDS : 0);
+        hipLaunchKernelGGL(k_inter4r, igrid, dim3(256), 0, s, b, S.dbinfo, rows, S.sp_flag, recon, X.tag, sync,
+                           (int)SW.zeroed(), levels ? X.d_lcnt : nullptr, levels ? 3 * LEVEL_IDS : 0);
         HIP_OK(hipGetLastError());
         // inter MBs of SP slices (a short launch when the batch has none)
-        hipLaunchKernelGGL(k_inter_sp, dim3(1024), dim3(256), 0, s, b, rows, (const int*)sp_flag, recon, X.tag);
+        hipLaunchKernelGGL(k_inter_sp, dim3(1024), dim3(256), 0, s, b, rows, (const int*)S.sp_flag, recon, X.tag);
         HIP_OK(hipGetLastError());
     }
     {
         Timed t(c, 1, s);
         uint16_t* lvl = levels ? X.d_lvl : nullptr;
-        int* pband = sync + 1 + (size_t)P * H + 32;             // after the zeroed words
-        int* lbar = sync + 1 + (size_t)P * H + 23;               // k_intra_levels' barrier (9 ints)
+        int* pband = sync + SW.pband();                         // after the zeroed words
+        int* lbar = sync + SW.barrier();                        // k_intra_levels' barrier
         const int lmax = levels ? level_launches((size_t)P * W * HB) : 0;
         if (knobs().verbose) fprintf(stderr, "h264r: %d intra levels from lists, %d pictures\n", lmax, P);
         if (levels) {
-            int* lvsync = sync + 1 + (size_t)P * H + 2;
+            int* lvsync = sync + SW.level();
             int* lcount = X.d_lcnt;
             int* lbase = lcount + LEVEL_IDS;
             int* lcursor = lbase + LEVEL_IDS;
@@ -645,7 +604,8 @@ static int deblock_launch(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
     const h264r_batch& b = S.b;
     const int W = b.width_mbs, H = b.height_mbs, P = b.num_pics, HB = rows.y - rows.x;
     const int npairs = (HB + 1) / 2;
-    int* dsync = S.sync + 1 + (size_t)P * H + 5;
+    const SyncWords SW{P, H};
+    int* dsync = S.sync + SW.tickets_y();
     if (c->debug & H264R_DBG_NO_DEBLOCK) {
         hipLaunchKernelGGL(k_untile, dim3((W * HB * 32 + 255) / 256, P), dim3(256), 0, s, b, rows, (const uint8_t*)S.recon);
         HIP_OK(hipGetLastError());
@@ -655,7 +615,7 @@ static int deblock_launch(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
     if (!c->nxcc) {                  // XCDs of the device: the deblocking kernels' placement
         int nx = 1;
         if (hipDeviceGetAttribute(&nx, hipDeviceAttributeNumberOfXccs, c->device) != hipSuccess) nx = 1;
-        c->nxcc = std::max(1, std::min(nx, 8));
+        c->nxcc = std::max(1, std::min(nx, SYNC_XCDS));         // a ticket set has SYNC_XCDS counters
     }
     if (sched == 1 && knobs().verbose) {
         static bool once = false;
@@ -679,7 +639,7 @@ static int deblock_launch(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
             HIP_OK(hipEventRecord(c->ev_fork, s));
             HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
             hipLaunchKernelGGL(k_deblock2c, dim3(grid), dim3(64), 0, c->side, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb),
-                               dsync + 9, c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
+                               S.sync + SW.tickets_c(), c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
             HIP_OK(hipGetLastError());
             hipLaunchKernelGGL(k_deblock2y, dim3(grid), dim3(64), 0, s, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb),
                                dsync, c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
@@ -730,12 +690,13 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
     const size_t nmb = (size_t)W * H;
     const bool wait_test = (c->debug & H264R_DBG_WAIT_TEST) != 0;
     // chunks of the overlapped schedule: each of >= 64 x 68 picture-MB-rows
-    int nch = (c->debug & H264R_DBG_OVERLAP) ? std::max(K.overlap, 4) : K.overlap;
+    static_assert(OVERLAP_MAX >= 4, "H264R_DBG_OVERLAP asks for 4 chunks");
+    int nch = (c->debug & H264R_DBG_OVERLAP) ? std::max(K.overlap, 4) : K.overlap;     // <= OVERLAP_MAX (knobs())
     nch = std::min(nch, (int)std::min<int64_t>(P, (int64_t)P * HB / (64 * 68)));
     if (nch < 2 || wait_test || (c->debug & H264R_DBG_NO_DEBLOCK)) nch = 1;
     const int chunk_min = P / nch;
     int st;
-    if ((st = dev_resize(&X.d_dbinfo, &X.c_dbinfo, (size_t)P * nmb * DBINFO_BYTES))) return st;
+    if ((st = dev_resize(&X.d_dbinfo, &X.c_dbinfo, (size_t)P * nmb * sizeof(DbInfo)))) return st;
     // the reconstruction kernels write the MB-tiled samples (device_common.h), the
     // deblocking kernel (or k_untile) turns them into the output planes
     if ((st = dev_resize(&X.d_recon, &X.c_recon, (size_t)P * nmb * 384))) return st;
@@ -768,13 +729,15 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
             *ep = 0;
         }
     }
-    const size_t sync_n = (size_t)nch * sync_ints(chunk_min + 1, H);
-    {
-        // each stage's k_inter4r zeroes its sync words; fresh memory is zeroed once, so no stale
-        // inter flag can carry a live tag
-        const size_t cap_before = X.c_sync;
-        if ((st = dev_resize(&X.d_sync, &X.c_sync, sync_n))) return st;
-        if (X.c_sync != cap_before) HIP_OK(hipMemsetAsync(X.d_sync, 0, X.c_sync * sizeof(int), s));
+    // a sync region per chunk, sized for the largest chunk; each stage's k_inter4r zeroes its own
+    // words, and k_level writes its pband words before k_intra_pic reads them
+    const size_t sync_stride = SyncWords{chunk_min + 1, H}.total();
+    if ((st = dev_resize(&X.d_sync, &X.c_sync, (size_t)nch * sync_stride))) return st;
+    if (!X.d_sptag) {
+        int* t = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&t), OVERLAP_MAX * sizeof(int)) != hipSuccess) return H264R_ENOMEM;
+        if (hipMemsetAsync(t, 0, OVERLAP_MAX * sizeof(int), s) != hipSuccess) { (void)hipFree(t); return H264R_EDEVICE; }
+        X.d_sptag = t;
     }
     // H264R_DBG_WAIT_TEST: every intra-walk wait asks for progress no row reaches, under a
     // 10 ms bound -- the launch must drain and h264r_check report H264R_EDEVICE
@@ -809,9 +772,9 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
     if (c->timing) c->timed_launches++;
     for (int k = 0, p0 = 0; k < nch; ++k) {
         const int n = P / nch + (k < P % nch ? 1 : 0);
-        Stage S{nch > 1 ? sub_batch(b, p0, n) : b, reinterpret_cast<h264r::DbInfo*>(X.d_dbinfo + (size_t)p0 * nmb * DBINFO_BYTES),
+        Stage S{nch > 1 ? sub_batch(b, p0, n) : b, reinterpret_cast<DbInfo*>(X.d_dbinfo) + (size_t)p0 * nmb,
                 X.d_recon + (size_t)p0 * nmb * 384,
-                X.d_sync + (size_t)k * sync_ints(chunk_min + 1, H)};
+                X.d_sync + (size_t)k * sync_stride, X.d_sptag + k};
         if ((st = recon_launches(c, S, s, rows, X, levels, K.coop && nch == 1))) return st;
         hipStream_t ds = s;
         if (nch > 1) {
@@ -1012,13 +975,17 @@ static bool chroma_out_ok(const h264r_ctx* c, const h264r_batch* b)
     return c->fmt == 0 || (b->out_u && b->out_v);
 }
 
+// what every batch entry point requires of its context and batch
+static bool batch_ok(const h264r_ctx* c, const h264r_batch* b)
+{
+    return c && b && b->num_pics > 0 && b->width_mbs > 0 && b->height_mbs > 0 && b->width_mbs <= c->max_w &&
+           b->height_mbs <= c->max_h && b->slice_stride > 0 && b->mbs && b->levels && b->mv && b->ref_idx && b->slices &&
+           b->pics && b->quant && b->out_y && chroma_out_ok(c, b) && stride_ok(b);
+}
+
 int h264r_decode_batch(h264r_ctx* c, const h264r_batch* b, void* stream)
 {
-    if (!c || !b || b->num_pics <= 0 || b->width_mbs <= 0 || b->height_mbs <= 0 ||
-        b->width_mbs > c->max_w || b->height_mbs > c->max_h || b->slice_stride <= 0 || !b->mbs || !b->levels ||
-        !b->mv || !b->ref_idx || !b->slices || !b->pics || !b->quant || !b->out_y || !chroma_out_ok(c, b) ||
-        !stride_ok(b))
-        return H264R_EINVAL;
+    if (!batch_ok(c, b)) return H264R_EINVAL;
     (void)hipSetDevice(c->device);
     h264r_batch bb = *b;
     if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes;
@@ -1034,11 +1001,7 @@ int h264r_decode_batch(h264r_ctx* c, const h264r_batch* b, void* stream)
 
 int h264r_decode_batch_rows(h264r_ctx* c, const h264r_batch* b, int row0, int row1, void* stream)
 {
-    if (!c || !b || row0 < 0 || row1 <= row0 || row1 > b->height_mbs) return H264R_EINVAL;
-    if (!b->mbs || !b->levels || !b->mv || !b->ref_idx || !b->slices || !b->pics || !b->quant || !b->out_y ||
-        !chroma_out_ok(c, b) || b->num_pics <= 0 || b->width_mbs <= 0 || b->width_mbs > c->max_w ||
-        b->height_mbs > c->max_h || b->slice_stride <= 0 || !stride_ok(b))
-        return H264R_EINVAL;
+    if (!batch_ok(c, b) || row0 < 0 || row1 <= row0 || row1 > b->height_mbs) return H264R_EINVAL;
     (void)hipSetDevice(c->device);
     h264r_batch bb = *b;
     if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes;
@@ -1406,7 +1369,6 @@ int h264r_picture_end(h264r_ctx* c, uint8_t* y, uint8_t* u, uint8_t* v, int keep
 
 #ifdef H264R_TRACE_INTRA
 // Diagnostic build only: copy the per-MB timing trace of k_intra_levels to the host.
-extern "C" __global__ void k_intra_trace_dump(unsigned long long* out, unsigned* n);
 extern "C" int h264r_trace_intra_dump(unsigned long long* out_host, unsigned* n_host)
 {
     unsigned long long* d = nullptr;

@@ -37,6 +37,7 @@
 // workgroup of C422_WAVES waves per picture, wave w taking MB rows w, w + C422_WAVES, ..., with
 // per-row progress in LDS.  Every wait is bounded (WaitClock).
 #include "device_common.h"
+#include "kernels.h"
 #include "mb_deblock.h"
 
 namespace h264r {
@@ -212,7 +213,7 @@ DEV void c422_mb(const h264r_batch& b, const Geom& g, int pic, int addr, int lan
                 const int mvx = (int16_t)(mv & 0xFFFF), mvy = (int16_t)(mv >> 16);
                 const int slot = sl->ref_slot[l][ri[l] & 15];
                 const uint8_t* ref = (slot >= 0 && slot < H264R_MAX_SLOTS) ? tab[3 * slot + 1 + p] : nullptr;
-                if (!ref) { __hip_atomic_store(err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
+                if (!ref) { __hip_atomic_store(err, DEV_ERR_FORMAT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
                 const int xf = mvx & 7, yf = (mvy & 3) << 1;
                 const int yi = mby * 16 + y + (mvy >> 2);
                 const int y0c = clip3(0, Hc - 1, yi), y1c = clip3(0, Hc - 1, yi + 1);
@@ -269,7 +270,7 @@ extern "C" __global__ __launch_bounds__(256) void k_c422_inter(h264r_batch b, in
     const h264r_mb m = load_mb_const(b.mbs + (size_t)pic * g.nmb + addr);
     if (mb_is_intra(m) && m.mb_type != H264R_I_PCM) return;              // k_c422_intra
     if ((ld_const(&b.slices[(size_t)pic * b.slice_stride + m.slice]) & 255) == H264R_SLICE_SP && lane == 0)
-        __hip_atomic_store(err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // SP is 4:2:0 only
+        __hip_atomic_store(err, DEV_ERR_FORMAT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // SP is 4:2:0 only
     c422_mb(b, g, pic, addr, lane, ws[wave], m, 0, err);
 }
 

@@ -32,6 +32,7 @@
 // rows 13..15 (chroma 5..7) of the row above after filtering its top edge;
 // only the picture's last row writes its own bottom rows.  A sample is stored
 // once, when final, by exactly one wave.
+#include "kernels.h"
 #include "mb_deblock.h"
 
 using namespace h264r;
@@ -78,7 +79,9 @@ extern "C" void h264r_db_trace_copy(void* dst) { (void)hipMemcpyFromSymbol(dst, 
 #endif
 
 // hb: hand-off records [pic][pair][W][32] granules {RingEntry dword, epoch};
-// sync[0]: ticket counter; epoch: this launch's tag (never 0: hb is zeroed when allocated).
+// sync: the region's luma ticket set (sync_words.h); epoch: this launch's tag (never 0: hb is
+// zeroed when allocated).
+static_assert(HANDOFF_BYTES == 32 * sizeof(uint64_t), "the host sizes hb by HANDOFF_BYTES per MB");
 #ifndef H264R_DB_WAVES
 #define H264R_DB_WAVES 1                    // minimum waves per SIMD asked of the register allocator
 #endif
@@ -110,7 +113,7 @@ extern "C" __global__ __launch_bounds__(64, H264R_DB_WAVES) void k_deblock(h264r
     if (lane == 0) tk = atomicAdd(&sync[xcc], 1);
     const int ticket = __builtin_amdgcn_readfirstlane(tk);
     if (ticket >= items) {
-        xcd_drain_check(sync, sync + 8, nx, [&](int k) { return (b.num_pics - k + nx - 1) / nx * npairs; }, err);
+        xcd_drain_check(sync, sync + TICKET_DRAIN, nx, [&](int k) { return (b.num_pics - k + nx - 1) / nx * npairs; }, err);
         return;
     }
     TRACE(unsigned long long tr_start = __builtin_amdgcn_s_memrealtime();)
@@ -253,7 +256,7 @@ extern "C" __global__ __launch_bounds__(64, H264R_DB_WAVES) void k_deblock(h264r
         // a band that starts below row 0 must not be filtered across its top edge (idc 1 or
         // a slice edge with idc 2): its top-edge strengths (bs[16..19] = info dword 4) are 0
         if (r == R0 && R0 > 0 && act && hl == 4 && pf_i != 0)
-            __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(err, DEV_ERR_BAND_EDGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (t + 1 < steps) prefetch(t + 1);
         wave_sync();
         TRACE({ asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t2 = __builtin_amdgcn_s_memtime(); tph[0] += t2 - ta; tm = t2; })

@@ -66,7 +66,7 @@
 // (chroma 7) of MB (x, y-1) after filtering its own top edge (into the upper unit's
 // staging inside the band, into UpLds for the band's first row).  The launch's last row
 // stages its own bottom rows.
-#include "launch_cfg.h"
+#include "kernels.h"
 #include "mb_deblock.h"
 #include "mb_deblock2.h"
 
@@ -93,6 +93,7 @@ constexpr int SG = H264R_DB2_SG;
 static_assert(SG == 4 || SG == 2, "H264R_DB2_SG");
 static_assert(UNITS % BAND == 0, "a band divides the wave's units");
 constexpr int RECG = 24;               // granules per MB record: [consumer lane c 0..3][i 0..5]
+static_assert(HANDOFF2_BYTES == 2 * RECG * sizeof(uint64_t), "the host sizes hb by HANDOFF2_BYTES per MB column");
 constexpr int AUX_SC1 = 16;            // buffer-op cache policy: sc1 (write-through store, L2-served load)
 constexpr int RSRC_W3 = 0x00020000;    // buffer descriptor word 3 (gfx9 raw buffer, range-checked)
 constexpr uint32_t OOB = 0x80000000u;  // added to an offset: past every range (loads 0, stores dropped)
@@ -236,7 +237,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
     if (threadIdx.x == 0) tk = atomicAdd(counter, 1);
     const int ticket = __builtin_amdgcn_readfirstlane(tk);
     if (ticket >= items) {
-        xcd_drain_check(sync, sync + 8, nx, [&](int k) { return (ngroups - k + nx - 1) / nx * nbands; }, err);
+        xcd_drain_check(sync, sync + TICKET_DRAIN, nx, [&](int k) { return (ngroups - k + nx - 1) / nx * nbands; }, err);
         return;
     }
     const int band = ticket / ngx, grp = (ticket - band * ngx) * nx + xcc;
@@ -562,7 +563,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
         // a launch that starts below row 0 must not be filtered across its top edge (idc 1, or a
         // slice edge with idc 2): its top-edge strengths (bs[16..19] = info dword 4) are 0
         if (R0 > 0 && band == 0 && __builtin_amdgcn_readfirstlane(__any(rb == 0 && xok && inf[4] != 0)))
-            __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(err, DEV_ERR_BAND_EDGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         wave_sync();                             // V(x) of every unit is in LDS
         TRACE({ const unsigned long long t2 = __builtin_amdgcn_s_memtime(); tph[1] += t2 - tm; tm = t2; })
         // the late pairs of MB x-1 (luma dword 3, chroma dword 1), final after V(x) (at x = W:

@@ -49,6 +49,7 @@
 // sets the context's error word for each of them (h264r_check reports it): a device-resident
 // batch reaches no host check.
 #include "device_common.h"
+#include "kernels.h"
 #include "sp_math.h"
 #include "wp_math.h"
 
@@ -494,7 +495,7 @@ DEV int inter_sample(const MPic& P, int r, int pl, int x, int y, int* err)
         rw[l] = fmb ? rr >> 1 : rr;
         const int slot = rw[l] < H264R_MAX_REFS ? sl.ref_slot[l][rw[l]] : -1;
         const uint8_t* base = slot >= 0 && slot < H264R_MAX_SLOTS ? P.tab[slot * 3 + pl] : nullptr;
-        if (!base) { __hip_atomic_store(err, 5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
+        if (!base) { __hip_atomic_store(err, DEV_ERR_MBAFF_REF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
         const uint32_t mvw = P.mv[l * P.mplane + idx];
         const int vx = (mbx * 4 + i) * 16 + (int16_t)(mvw & 0xFFFF);
         const int vy = (row4 + j) * 16 + (int16_t)(mvw >> 16);
@@ -900,7 +901,7 @@ DEV void edge_flags(const MPic& P, int r, DbLds& D, int h, int row0, int* err)
     if (idc == 0) { fl = Ln >= 0; ft = Un >= 0; }
     else if (idc == 2) { fl = Ln >= 0 && P.mbs[Ln].slice == q.slice; ft = Un >= 0 && P.mbs[Un].slice == q.slice; }
     if (ft && Un / P.wmb < row0) {                                         // the band's contract (above)
-        __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(err, DEV_ERR_BAND_EDGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ft = false;
     }
     for (int c = 0; c < 2; ++c) {
@@ -1023,7 +1024,7 @@ extern "C" __global__ __launch_bounds__(256) void k_mbaff_inter(h264r_batch b, i
         sl.slice_type == H264R_SLICE_SI || ((m.flags ^ P.mbs[other].flags) & H264R_MBF_FIELD) ||
         (sp && ((m.flags & H264R_MBF_T8x8) || sl.qs_y > 51 || sl.qs_c[0] < 0 || sl.qs_c[0] >= 6 || sl.qs_c[1] < 0 ||
                 sl.qs_c[1] >= 6))) {
-        if (t == 0) atomicOr(err, 8);
+        if (t == 0) atomicOr(err, DEV_ERR_MBAFF_REFUSED);
         return;
     }
     const bool pcm = m.mb_type == H264R_I_PCM;

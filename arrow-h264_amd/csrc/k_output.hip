@@ -19,8 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "h264r_output.h"
-#include "output_job.h"
+#include "kernels.h"
 
 namespace h264r {
 
@@ -99,7 +98,7 @@ k_output(OutJob job, const h264r_out_frame* __restrict__ frames, uint8_t* dst, i
             ok = ok && u0p && v0p && (!pair || (u1p && v1p));
         }
         if (!ok) {
-            if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) atomicOr(err, OUT_ERR);
+            if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) atomicOr(err, DEV_ERR_OUTPUT);
             continue;
         }
         // the rows of the missing parity of an unpaired field: 128 (storable_picture::clear)

@@ -14,6 +14,7 @@
 // tickets in band-major order from an atomic counter, so every workgroup only
 // ever waits on a ticket taken earlier by a resident workgroup: no deadlock
 // whatever the dispatch order or residency.  Every wait is bounded.
+#include "kernels.h"
 #include "mb_intra.h"
 
 // k_intra_levels' register budget: 6 waves/SIMD = 80 VGPRs, no spill (LDS allows 7; at the
@@ -22,8 +23,6 @@
 #ifndef H264R_LVL_WAVES
 #define H264R_LVL_WAVES 6
 #endif
-#define H264R_LEVEL_MAX_MBS 65536           // k_level keeps a picture's intra bitmap in LDS
-#define H264R_LEVEL_LISTS 64                // levels 1 .. this many get per-level MB lists
 #ifndef H264R_INTRA_PAIRS
 #define H264R_INTRA_PAIRS 1                 // k_intra_levels reconstructs pairable MBs two per wave (intra_pair_i4)
 #endif
@@ -31,9 +30,6 @@
 #undef H264R_INTRA_PAIRS
 #define H264R_INTRA_PAIRS 0                 // the trace times one MB per item
 #endif
-// Two lists per level: id 2 L = its pairable MBs (intra_pairable: I_4x4, not lossless), id
-// 2 L + 1 the others, laid out in id order; count / base / cursor arrays of LEVEL_IDS ints.
-constexpr int LEVEL_IDS = 2 * (H264R_LEVEL_LISTS + 1);
 
 using namespace h264r;
 
@@ -62,13 +58,10 @@ DEV void intra_trace_put(unsigned long long t0, unsigned long long w, const unsi
 
 namespace {
 
-#ifndef H264R_WALK_ROWS
-#define H264R_WALK_ROWS 8                   // MB rows per band (h264r_host.hip sizes the launch with it)
-#endif
 #ifndef H264R_WALK_WAVES
 #define H264R_WALK_WAVES 8                  // minimum waves per SIMD asked of the register allocator (<= 64 VGPRs; profiles/r03s2_b_ab.txt)
 #endif
-constexpr int WAVES = H264R_WALK_ROWS;      // rows per band, one wave each
+constexpr int WAVES = H264R_WALK_ROWS;      // MB rows per band (kernels.h), one wave each
 
 DEV void publish_lds(int* counter, int value, int lane)
 {
@@ -105,7 +98,8 @@ DEV bool wait_for(int* counter, int need, int* err, int& seen)
 }  // namespace
 
 // One (band, picture) ticket: wave `wave` walks MB row r0 + wave of the band.
-// sync: [0] ticket counter, [1 ..] per (picture, row) progress; zeroed before every launch.
+// sync: the launch sequence's sync region (sync_words.h): its ticket counter and the per
+// (picture, row) progress words, zeroed before every launch.
 // Bit `band` of a picture's band mask (k_level: bit b for band b; all bits set, or none, when the
 // picture has more than 31 bands -- a shift by 32 or more is not defined in C++)
 DEV bool band_bit(int pb, int band) { return band >= 32 ? pb != 0 : ((pb >> band) & 1) != 0; }
@@ -127,7 +121,7 @@ DEV void walk_ticket(const h264r_batch& b, int* sync, int* err, Scratch* scratch
     if (r >= r1) return;
     // the band above has nothing deeper than the lists: its rows are final already
     const bool above_done = lvl && band > 0 && !band_bit(pband[pic], band - 1);
-    int* gprog = sync + 1 + (size_t)pic * g.hmb;
+    int* gprog = sync + SyncWords{b.num_pics, g.hmb}.progress(pic);
     const bool last_row = r == r1 - 1 && r1 < R1;
     Scratch& S = scratch[wave];
     const h264r_mb* mbs = b.mbs + (size_t)pic * g.nmb;
@@ -236,7 +230,7 @@ extern "C" __global__ __launch_bounds__(64 * H264R_WALK_ROWS, H264R_WALK_WAVES) 
     __shared__ uint32_t tap4[INTRA_TAPS];
     __shared__ int lprog[WAVES];
     __shared__ int ticket;
-    if (threadIdx.x == 0) ticket = atomicAdd(&sync[0], 1);
+    if (threadIdx.x == 0) ticket = atomicAdd(&sync[SyncWords::intra_ticket()], 1);
     if (threadIdx.x < WAVES) lprog[threadIdx.x] = 0;
     __syncthreads();
     if (lvl && !band_bit(pband[ticket % b.num_pics], ticket / b.num_pics)) return;       // (block-uniform)
@@ -268,14 +262,13 @@ extern "C" __global__ __launch_bounds__(64 * H264R_WALK_ROWS, H264R_WALK_WAVES) 
 // walk whole.  It replaced a walk of the rows in lock step (one thread per row, one workgroup
 // barrier per MB step, x + 2y steps): 88 us per 1080p picture in the latency chain, 148 us per
 // 1024-picture batch (profiles/r05_ac_latency_kernels.txt, r04_ak_kernel_stats_b1024.csv).
-// lcount[id] (id 2 L + c, L = 1 .. H264R_LEVEL_LISTS, c = 0 pairable): intra MBs of level L over
+// lcount[id] (id 2 L + c, L = 1 .. LEVEL_LISTS, c = 0 pairable): intra MBs of level L over
 // the batch (zeroed per batch); k_level_scatter turns them into the lists.
-constexpr int LEVEL_LDS = 40960;            // (W + 2) x (rows + 1) level bytes (h264r_host.hip checks)
 extern "C" __global__ __launch_bounds__(1024) void k_level(h264r_batch b, uint16_t* lvl, int* lvsync, int* lcount, int2 rows,
                                                           int deep_cut, int lmax, int* pband)
 {
-    __shared__ uint64_t bits[H264R_LEVEL_MAX_MBS / 64];   // intra (not PCM) MBs of the picture
-    __shared__ uint64_t pbits[H264R_LEVEL_MAX_MBS / 64];  // the pairable ones among them
+    __shared__ uint64_t bits[LEVEL_MAX_MBS / 64];   // intra (not PCM) MBs of the picture
+    __shared__ uint64_t pbits[LEVEL_MAX_MBS / 64];  // the pairable ones among them
     __shared__ uint8_t lv[LEVEL_LDS];                     // level of band row r, MB x at (r + 1) * (W + 2) + x + 1
     __shared__ int hist[LEVEL_IDS];
     __shared__ int pdeep, sband;
@@ -353,7 +346,7 @@ extern "C" __global__ __launch_bounds__(1024) void k_level(h264r_batch b, uint16
             out[m] = (uint16_t)L;
             deepest = max(deepest, L);
             if (L > lmax) atomicOr(&sband, wb > 31 ? -1 : 1 << (rr / wbh));
-            if (L >= 1 && L <= H264R_LEVEL_LISTS) atomicAdd(&hist[2 * L + !((pbits[m >> 6] >> (m & 63)) & 1)], 1);
+            if (L >= 1 && L <= LEVEL_LISTS) atomicAdd(&hist[2 * L + !((pbits[m >> 6] >> (m & 63)) & 1)], 1);
         }
         for (int d = 32; d >= 1; d >>= 1) deepest = max(deepest, __shfl_xor(deepest, d));
         if (lane == 0 && deepest) atomicMax(&pdeep, deepest);
@@ -368,13 +361,13 @@ extern "C" __global__ __launch_bounds__(1024) void k_level(h264r_batch b, uint16
         return;
     }
     if (tid == 0) pband[pic] = sband;
-    if (tid == 0 && deepest) atomicMax(&lvsync[1], deepest);
+    if (tid == 0 && deepest) atomicMax(&lvsync[LEVEL_DEEPEST], deepest);
     for (int i = tid + 2; i < LEVEL_IDS; i += nt)
         if (hist[i]) atomicAdd(&lcount[i], hist[i]);
 }
 
 // The per-level MB lists: lbase[L] = exclusive prefix of lcount over levels (each
-// k_level_scatter workgroup scans them itself), then every intra MB of level 1 .. H264R_LEVEL_LISTS appends
+// k_level_scatter workgroup scans them itself), then every intra MB of level 1 .. LEVEL_LISTS appends
 // pic * nmb + addr to its level's list (k_level_scatter: a workgroup counts its MBs per
 // level in LDS and reserves each level's range with one global atomic).
 // lcount, lbase, lcursor: LEVEL_IDS ints each.
@@ -429,9 +422,9 @@ extern "C" __global__ __launch_bounds__(1024) void k_level_scatter(h264r_batch b
             const int m = base + k * 1024 + tid;
             const int lv = m < m1 ? lp[m] : 0;
             // the list id: 2 L for a pairable MB (intra_pairable; k_level counted the same), else 2 L + 1
-            const uint32_t w0 = lv >= 1 && lv <= H264R_LEVEL_LISTS ? *reinterpret_cast<const uint32_t*>(&mbs[m]) : 0u;
+            const uint32_t w0 = lv >= 1 && lv <= LEVEL_LISTS ? *reinterpret_cast<const uint32_t*>(&mbs[m]) : 0u;
             const bool pr = (w0 & 255) == H264R_I_4x4 && !((w0 >> 8) & H264R_MBF_BYPASS);
-            L[k] = lv >= 1 && lv <= H264R_LEVEL_LISTS ? 2 * lv + !pr : 0;
+            L[k] = lv >= 1 && lv <= LEVEL_LISTS ? 2 * lv + !pr : 0;
         }
 #pragma unroll
         for (int k = 0; k < SCATTER_PER; ++k) rank[k] = L[k] ? atomicAdd(&cnt[L[k]], 1) : 0;
@@ -455,24 +448,26 @@ extern "C" __global__ __launch_bounds__(1024) void k_level_scatter(h264r_batch b
 // and every workgroup waits on the top counter, then acquires.  One counter for all the
 // ~1000 arrivals had serialised them (MI355X_MICROARCH.md price list 'barrier-counter' vs
 // 'barrier-xcd', 'fanin').  Each wave takes its level's items grid-stride.
-// bar: [0..7] shard counters, [8] top counter, zeroed per batch (by k_inter4r); L = 1, 2, ...
+// bar: the region's level barrier (sync_words.h: shard counters, then the top counter), zeroed
+// per batch (by k_inter4r); L = 1, 2, ...
 DEV bool grid_barrier(int* bar, int L, int* err)
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __shared__ int ok;
     if (threadIdx.x == 0) {
-        const int G = (int)gridDim.x, sh = (int)blockIdx.x & 7;
-        const int nsh = (G - sh + 7) / 8, nshards = min(G, 8);           // workgroups of my shard; shards
+        static_assert((SYNC_XCDS & (SYNC_XCDS - 1)) == 0, "the shard of a workgroup is a mask of its index");
+        const int G = (int)gridDim.x, sh = (int)blockIdx.x & (SYNC_XCDS - 1);
+        const int nsh = (G - sh + SYNC_XCDS - 1) / SYNC_XCDS, nshards = min(G, SYNC_XCDS);   // workgroups of my shard; shards
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (__hip_atomic_fetch_add(&bar[sh], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == L * nsh - 1) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-            __hip_atomic_fetch_add(&bar[8], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&bar[BARRIER_TOP], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         WaitClock wc;
         ok = 1;
-        while (__hip_atomic_load(&bar[8], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < L * nshards) {
+        while (__hip_atomic_load(&bar[BARRIER_TOP], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < L * nshards) {
             __builtin_amdgcn_s_sleep(2);
             if (wait_give_up(err, wc)) { ok = 0; break; }
         }
@@ -506,7 +501,7 @@ extern "C" __global__ __launch_bounds__(256, H264R_LVL_WAVES) void k_intra_level
     const Geom g = make_geom(b.width_mbs, b.height_mbs);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int nw = (int)gridDim.x * 4, gw = (int)blockIdx.x * 4 + wave;
-    const int deepest = __hip_atomic_load(&lvsync[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int deepest = __hip_atomic_load(&lvsync[LEVEL_DEEPEST], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int top = min(lmax, deepest);
     for (int L = 1; L <= top; ++L) {
         // the MBs of level L, wave-strided over its items (entry = pic * nmb + addr): the pairs of
@@ -522,7 +517,7 @@ extern "C" __global__ __launch_bounds__(256, H264R_LVL_WAVES) void k_intra_level
                 // one is a broken list, flagged as a device error (h264r_check)
                 if (!intra_pair_i4(b, g, list[base + 2 * e], list[base + 2 * e + 1], ln, scratch[wave], scratch[4 + wave],
                                    tap4, recon))
-                    __hip_atomic_store(err, 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(err, DEV_ERR_SCHEDULE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 continue;
             }
             const uint32_t k = list[base + np + e];

@@ -6,7 +6,7 @@
 //           neighbours).  Motion is read as the parser left it ({mv, ref_idx} per list) and
 //           RefPicList[l][ref_idx] resolved to a DPB slot through an LDS copy of the
 //           picture's slice tables.
-#include "launch_cfg.h"
+#include "kernels.h"
 #include "mb_inter_sp.h"
 
 using namespace h264r;
@@ -73,8 +73,8 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // nz2)) for the kernels after it -- no memset launches per batch (the latency chain paid ~20 us
 // for them, profiles/r05_ac_latency_kernels.txt).
 // sp_flag: set to the launch tag when an inter MB of an SP slice was met (k_inter_sp then runs; a
-// tag, not a flag, so nothing has to zero it between launch sequences -- it lies outside the
-// words this kernel zeroes).
+// tag, not a flag, so nothing has to zero it between launch sequences -- the word is the host's
+// own array of SP tags, outside the sync region this kernel zeroes, and only ever holds tags).
 // Grid (8 * ceil(groups / (8 * per)), pictures), XCD-aware: workgroups go round-robin to the 8
 // XCDs in launch order, so blockIdx.x % 8 is the XCD and it takes the 16-MB groups of band
 // blockIdx.x % 8 (one eighth of the MB rows) of every picture: an XCD's motion
@@ -209,7 +209,7 @@ extern "C" __global__ __launch_bounds__(256) void k_derive444(h264r_batch b, int
     }
     for (int64_t i = t0; i < P * b.slice_stride; i += nt) {
         h264r_slice x = b.slices[i];
-        if (x.slice_type == H264R_SLICE_SP) atomicOr(err, 4);     // SP slices: 4:2:0 only (Extended profile)
+        if (x.slice_type == H264R_SLICE_SP) atomicOr(err, DEV_ERR_FORMAT);     // SP slices: 4:2:0 only (Extended profile)
         if (pl) {
             for (int l = 0; l < 2; ++l)
                 for (int r = 0; r < H264R_MAX_REFS; ++r) {
@@ -242,5 +242,5 @@ extern "C" __global__ __launch_bounds__(256) void k_derive444(h264r_batch b, int
         refs[i] = b.ref_planes[tab * b.ref_planes_stride + 3 * slot + qpl];
     }
     for (int64_t i = t0; i < P; i += nt)
-        if (b.pics[i].structure != H264R_FRAME) atomicOr(err, 1);
+        if (b.pics[i].structure != H264R_FRAME) atomicOr(err, DEV_ERR_NOT_FRAME);
 }

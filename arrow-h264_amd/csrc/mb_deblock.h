@@ -11,7 +11,7 @@
 // filter_normal (deblock.cc:327-415), and written back.
 #pragma once
 #include "device_common.h"
-#include "launch_cfg.h"
+#include "kernels.h"
 
 namespace h264r {
 
@@ -72,19 +72,7 @@ DEV int bs_compare_one(const MotionRef& p, const MotionRef& q, int mvlim)
 
 DEV int special_slice(int t) { return t == H264R_SLICE_SP || t == H264R_SLICE_SI; }
 
-// Per-MB deblocking record, produced by k_inter for every MB (fully parallel) so
-// that the order-dependent walk only loads 48 bytes per MB.  bs[] folds the edge
-// enables of Deblock::strength (deblock.cc:236-278) into the strengths: a
-// disabled edge has bS 0.  bs[hor * 16 + edge * 4 + segment]; chroma edge 0 uses
-// luma edge 0, chroma edge 1 (sample 4) luma edge 2 (deblock.cc:430-433).
-struct DbInfo {
-    uint8_t  bs[32];
-    uint32_t par[9];       // [Y, Cb, Cr][left edge, top edge, internal edges]: edge_word()
-    uint32_t pad[3];
-};
-static_assert(sizeof(DbInfo) == 80, "DbInfo layout");
-constexpr int DBINFO_DWORDS = 20;
-constexpr int DEBLOCK2_UNITS = 64 / H264R_DB2_LPU;   // k_deblock2: (picture, MB row) units per wave
+// (the per-MB deblocking record DbInfo, which the host sizes its scratch by, is in kernels.h)
 
 // alpha | beta << 8 | tc0(bS 1..3) << 16 / 21 / 26 for one edge: filter_edge
 // deblock.cc:469-480 (qPav of the two MBs' QPs, indexA/B with MbQ's slice offsets),

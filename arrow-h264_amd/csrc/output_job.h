@@ -31,7 +31,6 @@ struct OutJob {
 
 constexpr int OUT_THREADS = 256;   // k_output: threads per workgroup
 constexpr int OUT_ITEMS = 4;       // 16-byte chunks per thread
-constexpr int OUT_ERR = 16;        // bit of the context's error word: a refused frame
 
 // 16-byte chunks a row of w bytes is cut into at most: its destination may start anywhere inside one
 inline __host__ __device__ int out_chunks_per_row(int w) { return (w + 15) / 16 + 1; }

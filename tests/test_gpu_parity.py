@@ -358,6 +358,19 @@ def test_gpu_batch_sp(L, dec, W, H, n, over):
     _batch_vs_oracle(L, dec, 3, W, H, n, sp_slices=1, **over)
 
 
+def test_gpu_sp_tag_across_shapes(L, dec):
+    """The SP tag word across launches of different shapes on one context: an SP batch, then a
+    batch of another size (other P and H) without SP slices, then that size with SP slices, every
+    picture of every call against the oracle.  The word lives in an array of its own that only
+    ever holds launch tags, so it still routes the SP slices' inter MBs to k_inter_sp and a launch
+    without SP slices does not confuse it.  While it lay behind the sync region, at an offset that
+    moves with P and H, a stale counter there could equal the current tag and make k_inter_sp run
+    a full pass for nothing: that pass only cost time, so this test cannot observe its removal."""
+    _batch_vs_oracle(L, dec, 3, 6, 4, 2, sp_slices=1)
+    _batch_vs_oracle(L, dec, 3, 5, 3, 3)
+    _batch_vs_oracle(L, dec, 3, 5, 3, 3, sp_slices=1)
+
+
 def test_gpu_batch_1080p_b_scaling(L, dec):
     """Config 4 size with explicit (non-flat) scaling matrices."""
     _batch_vs_oracle(L, dec, 4, 120, 68, 2, qm=21)
