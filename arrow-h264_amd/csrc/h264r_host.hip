@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1150,6 +1151,111 @@ int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_ou
     const int per = h264r::OUT_THREADS * h264r::OUT_ITEMS;
     const dim3 grid((unsigned)((items + per - 1) / per), (unsigned)std::min(num_frames, 65535), (unsigned)job.nplanes);
     hipLaunchKernelGGL(k_output, grid, dim3(h264r::OUT_THREADS), 0, s, job, frames, dst, c->d_err);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- RGB frames (h264r_output.h)
+int h264r_rgb_coefficients(int matrix, int full_range, int32_t out[6])
+{
+    // floor(real * 2^14 + 1/2) of the header's reals: cy, crv, cgu, cgv, cbu, yo
+    static const int32_t rows[3][2][6] = {
+        {{19077, 26149, -6419, -13320, 33050, 16}, {16384, 22970, -5638, -11700, 29032, 0}},   // BT.601
+        {{19077, 29372, -3494, -8731, 34610, 16}, {16384, 25802, -3069, -7670, 30402, 0}},     // BT.709
+        {{19077, 27503, -3069, -10657, 35091, 16}, {16384, 24160, -2696, -9361, 30825, 0}},    // BT.2020
+    };
+    if (!out || matrix < H264R_CSC_BT601 || matrix > H264R_CSC_BT2020 || (full_range != 0 && full_range != 1))
+        return H264R_EINVAL;
+    for (int k = 0; k < 6; ++k) out[k] = rows[matrix][full_range][k];
+    return H264R_OK;
+}
+
+// The layout of one RGB frame and the job k_output_rgb takes, from the geometry of desc->src.
+static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job)
+{
+    if (!d || d->src.layout != H264R_OUT_PLANAR || d->src.fake_chroma != 0) return H264R_EINVAL;
+    h264r_out_geom og;
+    const int st = output_plan(fmt, &d->src, &og, nullptr);
+    if (st != H264R_OK) return st;
+    if (d->matrix < H264R_CSC_BT601 || d->matrix > H264R_CSC_GBR ||
+        (d->chroma_up != H264R_UP_REPLICATE && d->chroma_up != H264R_UP_BILINEAR) ||
+        d->format < H264R_RGB_PACKED_U8 || d->format > H264R_RGB_PLANAR_F16 ||
+        (d->full_range != 0 && d->full_range != 1) || (d->bgr != 0 && d->bgr != 1) || d->alpha < 0 || d->alpha > 255)
+        return H264R_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(d->scale[k]) || !std::isfinite(d->bias[k])) return H264R_EINVAL;
+    if (d->matrix == H264R_CSC_GBR && fmt != 3) return H264R_EUNSUPPORTED;
+
+    const int64_t lw = og.luma[2], lh = og.luma[3];
+    const bool planar = d->format == H264R_RGB_PLANAR_U8 || d->format == H264R_RGB_PLANAR_F16;
+    const int64_t bpp = d->format == H264R_RGB_PACKED_U8 ? 3 : d->format == H264R_RGB_PACKED_U8X4 ? 4 :
+                        d->format == H264R_RGB_PLANAR_F16 ? 2 : 1;
+    const int64_t pa = d->src.pitch_align;
+    const int64_t pitch = pa > 1 ? (bpp * lw + pa - 1) / pa * pa : bpp * lw;
+    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * lh;
+    if (g) {
+        *g = h264r_rgb_geom{};
+        g->width = (int32_t)lw; g->height = (int32_t)lh;
+        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * lh; g->plane_pitch[k] = pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) {
+        h264r::RgbJob J{};
+        for (int k = 0; k < 3; ++k) J.plane_off[k] = planar ? k * pitch * lh : 0;
+        J.pitch = pitch;
+        J.frame_stride = frame_bytes;
+        J.lw = (int32_t)lw; J.lh = (int32_t)lh; J.x0 = og.luma[0]; J.y0 = og.luma[1];
+        J.cx0 = og.chroma[0]; J.cy0 = og.chroma[1]; J.cw = og.chroma[2]; J.ch = og.chroma[3];
+        J.lpitch = 16 * d->src.width_mbs;
+        J.cpitch = fmt == 3 ? J.lpitch : fmt ? J.lpitch / 2 : 0;
+        J.sub_h = fmt == 1 ? 2 : 1;
+        const bool bil = d->chroma_up == H264R_UP_BILINEAR;
+        J.mode = fmt == 0 ? h264r::RGB_MONO : fmt == 3 ? (d->matrix == H264R_CSC_GBR ? h264r::RGB_GBR : h264r::RGB_FULL) :
+                 !bil ? h264r::RGB_REP : fmt == 2 ? h264r::RGB_BIL1 : h264r::RGB_BIL2;
+        J.format = d->format; J.bgr = d->bgr; J.alpha = d->alpha;
+        if (d->matrix != H264R_CSC_GBR) {
+            int32_t k[6];
+            h264r_rgb_coefficients(d->matrix, d->full_range, k);
+            J.cy = k[0]; J.crv = k[1]; J.cgu = k[2]; J.cgv = k[3]; J.cbu = k[4]; J.yo = k[5];
+        }
+        for (int k = 0; k < 3; ++k) { J.scale[k] = d->scale[k]; J.bias[k] = d->bias[k]; }
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return rgb_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_rgb(h264r_ctx* c, const h264r_rgb_desc* desc, const h264r_out_frame* frames, int num_frames,
+                     void* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::RgbJob job;
+    const int st = rgb_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
+    if (job.format == H264R_RGB_PLANAR_F16 && ((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1))
+        return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.frame_stride = dst_frame_stride;
+    job.num_frames = num_frames;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    // ordered after the context's last launch, as h264r_output_frames is
+    if (c->last_stream && c->last_stream != s) {
+        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
+        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
+    }
+    c->last_stream = s;
+    const int units = job.lh * h264r::rgb_units_per_row(job.lw);
+    const int per = h264r::RGB_THREADS * h264r::RGB_ITEMS;
+    const dim3 grid((unsigned)((units + per - 1) / per), (unsigned)std::min(num_frames, 65535));
+    hipLaunchKernelGGL(k_output_rgb, grid, dim3(h264r::RGB_THREADS), 0, s, job, frames, static_cast<uint8_t*>(dst),
+                       c->d_err);
     HIP_OK(hipGetLastError());
     return H264R_OK;
 }

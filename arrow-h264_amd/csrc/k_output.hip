@@ -16,6 +16,8 @@
 // stores the first, OUT_THREADS apart so that a wave's loads and stores are contiguous.
 //
 // Grid: x = groups of OUT_THREADS * OUT_ITEMS windows of one plane, y = frames (strided), z = plane.
+//
+// Below it k_output_rgb, which writes the same frames as RGB; it has a comment of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -160,5 +162,312 @@ k_output(OutJob job, const h264r_out_frame* __restrict__ frames, uint8_t* dst, i
                 t.d[b - t.b0] = x;
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_output_rgb -- the RGB frames of include/h264r_output.h (its comment is the definition; the names
+// below are the header's).  One launch for every frame of a job, nothing but registers.
+//
+// The unit of work is RGB_UNIT = 16 horizontally consecutive pixels of one output row, counted from
+// the row's first pixel.  A whole unit costs one unaligned 16-byte luma load and, per chroma plane and
+// chroma row it needs, one 8-byte load (16 in 4:4:4) plus, under bilinear, the one sample that follows
+// (clamped to the crop's last column): exactly the bytes the definition names, so nothing outside the
+// crop -- let alone the plane -- is read.  The row's last unit, when the width is no multiple of 16,
+// fetches its samples bytewise with the same clamp.  Either way the unit then holds the same registers,
+// is converted by the same code to 16 bytes per channel, and those are interleaved in registers
+// (v_perm_b32) into the format's bytes: 48 (RGB24), 64 (RGBX), 16 per plane (planar u8) or 32 per
+// plane (binary16).  Where the unit is whole and its destination 16-byte aligned they leave as 16-byte
+// stores; elsewhere as dwords or bytes, never one outside the row.  A thread fetches RGB_ITEMS units
+// before it stores the first, RGB_THREADS apart, so that a wave's loads are contiguous.
+//
+// Grid: x = groups of RGB_THREADS * RGB_ITEMS units, y = frames (strided).
+namespace h264r {
+
+struct RgbUnit {
+    int r, x, n;               // output row, first pixel, pixels (0: no unit)
+    uint4 y;                   // 16 luma samples
+    uint4 ua, va, ub, vb;      // chroma rows A (j0) and B (j1, RGB_BIL2 only): SubWidthC 1: 16 samples;
+                               // SubWidthC 2: samples 0..7 in .x .y, the clamped sample 8 in .z
+};
+
+constexpr uint32_t RGB_GREY = 0x80808080u;
+
+// The row R of a plane of the woven frame: nullptr = a row of 128 (the missing parity of an unpaired field).
+__device__ __forceinline__ const uint8_t* rgb_row(const uint8_t* p0, const uint8_t* p1, int R, int pitch, int kind)
+{
+    const int fill_parity = kind == H264R_OUT_UNPAIRED_TOP ? 1 : kind == H264R_OUT_UNPAIRED_BOT ? 0 : -1;
+    if ((R & 1) == fill_parity) return nullptr;
+    const uint8_t* const p = (kind == H264R_OUT_FIELD_PAIR && (R & 1)) ? p1 : p0;
+    return p + (int64_t)(kind != H264R_OUT_FRAME ? R >> 1 : R) * pitch;
+}
+
+// cnt samples from s[first], indices clamped to last, bytewise: the partial unit's fetch
+__device__ __forceinline__ uint4 rgb_ld_clamped(const uint8_t* s, int first, int last, int cnt)
+{
+    // the nv samples that exist, off one address; the clamped ones behind them repeat the last
+    const uint8_t* const p = s + first;
+    const int nv = min(cnt, last - first + 1);
+    const uint32_t rep = (uint32_t)ld1(p + nv - 1) * 0x01010101u;
+    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int m = 0; m < 16; ++m)
+        if (m < nv) w[m >> 2] |= (uint32_t)ld1(p + m) << (8 * (m & 3));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int have = nv - 4 * q;                        // bytes of w[q] that exist
+        if (have < 4) w[q] |= have <= 0 ? rep : rep & (0xffffffffu << (8 * have));
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// One chroma row's samples for the unit at chroma column i0: s = the row at the crop's first column.
+__device__ __forceinline__ uint4 rgb_ld_chroma(const uint8_t* s, int i0, int cw, int mode, bool whole)
+{
+    if (!s) return make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
+    const bool wide = mode < RGB_REP;
+    if (!whole) return rgb_ld_clamped(s, i0, cw - 1, wide ? 16 : 9);
+    if (wide) return ld16u(s + i0);
+    const uint2 a = ld8u(s + i0);
+    const uint32_t next = mode >= RGB_BIL1 ? ld1(s + min(i0 + 8, cw - 1)) : 0u;
+    return make_uint4(a.x, a.y, next, 0u);
+}
+
+__device__ __forceinline__ int rgb_byte(const uint4& v, int k)
+{
+    const uint32_t w = (k >> 2) == 0 ? v.x : (k >> 2) == 1 ? v.y : (k >> 2) == 2 ? v.z : v.w;
+    return (int)((w >> (8 * (k & 3))) & 0xffu);
+}
+
+// clip255(v >> 17), clamped BEFORE the shift: min(max(v, 0), 2^25 - 1) >> 17 is the same number, and it
+// keeps the compiler from fusing shift and clamp of two pixels into gfx950's v_ashr_pk_u8_i32
+__device__ __forceinline__ int rgb_clip255_sh17(int v) { return (int)((uint32_t)min(max(v, 0), (256 << 17) - 1) >> 17); }
+
+// The unit's 16 pixels as 16 bytes per channel: c[0] = R, c[1] = G, c[2] = B.
+template <int MODE>
+__device__ __forceinline__ void rgb_convert(const RgbJob& J, const RgbUnit& t, uint32_t (&c)[3][4])
+{
+    if (MODE == RGB_GBR) {
+        c[0][0] = t.va.x; c[0][1] = t.va.y; c[0][2] = t.va.z; c[0][3] = t.va.w;
+        c[1][0] = t.y.x;  c[1][1] = t.y.y;  c[1][2] = t.y.z;  c[1][3] = t.y.w;
+        c[2][0] = t.ua.x; c[2][1] = t.ua.y; c[2][2] = t.ua.z; c[2][3] = t.ua.w;
+        return;
+    }
+    const int ky = 8 * J.cy;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[0][q] = c[1][q] = c[2][q] = 0;
+#pragma unroll
+    for (int k = 0; k < RGB_UNIT; ++k) {
+        // every factor fits 24 bits and every sum 27: v_mad_i32_i24
+        const int yt = __mul24(ky, rgb_byte(t.y, k) - J.yo) + 65536;
+        int r, g, b;
+        if (MODE == RGB_MONO) {
+            r = g = b = rgb_clip255_sh17(yt);
+        } else {
+            int cb8, cr8;
+            if (MODE == RGB_FULL) {
+                cb8 = 8 * rgb_byte(t.ua, k);
+                cr8 = 8 * rgb_byte(t.va, k);
+            } else {
+                const int m = k >> 1, m1 = (MODE != RGB_REP && (k & 1)) ? m + 1 : m;    // wh 2, or 1 and 1
+                const int hu = rgb_byte(t.ua, m) + rgb_byte(t.ua, m1), hv = rgb_byte(t.va, m) + rgb_byte(t.va, m1);
+                if (MODE == RGB_BIL2) {
+                    cb8 = 3 * hu + rgb_byte(t.ub, m) + rgb_byte(t.ub, m1);              // wv 3 and 1
+                    cr8 = 3 * hv + rgb_byte(t.vb, m) + rgb_byte(t.vb, m1);
+                } else {
+                    cb8 = 4 * hu;
+                    cr8 = 4 * hv;
+                }
+            }
+            const int cbd = cb8 - 1024, crd = cr8 - 1024;
+            r = rgb_clip255_sh17(yt + __mul24(J.crv, crd));
+            g = rgb_clip255_sh17(yt + __mul24(J.cgu, cbd) + __mul24(J.cgv, crd));
+            b = rgb_clip255_sh17(yt + __mul24(J.cbu, cbd));
+        }
+        c[0][k >> 2] |= (uint32_t)r << (8 * (k & 3));
+        c[1][k >> 2] |= (uint32_t)g << (8 * (k & 3));
+        c[2][k >> 2] |= (uint32_t)b << (8 * (k & 3));
+    }
+}
+
+// bytes s of the eight bytes hi:lo (selector byte values 0..3 = lo's bytes, 4..7 = hi's): v_perm_b32
+__device__ __forceinline__ uint32_t rgb_perm(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_perm(hi, lo, s); }
+
+// NDW dwords to d, of which the first nbytes are the row's: 16-byte stores where all of them are and d
+// allows it, else dwords, else bytes
+template <int NDW>
+__device__ __forceinline__ void rgb_store(uint8_t* d, const uint32_t (&w)[NDW], int nbytes)
+{
+    const unsigned mis = (unsigned)reinterpret_cast<uintptr_t>(d);
+    if (nbytes == 4 * NDW && !(mis & 15)) {
+#pragma unroll
+        for (int q = 0; q < NDW / 4; ++q)
+            reinterpret_cast<uint4*>(d)[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    } else if (nbytes == 4 * NDW && !(mis & 3)) {
+#pragma unroll
+        for (int q = 0; q < NDW; ++q) reinterpret_cast<uint32_t*>(d)[q] = w[q];
+    } else {
+#pragma unroll
+        for (int b = 0; b < 4 * NDW; ++b)
+            if (b < nbytes) d[b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+// channel bytes v (4 pixels) -> binary16 of float(v) * scale + bias: a multiplication, an addition, a
+// conversion, each rounded to nearest even on its own (no fused multiply-add: contraction is off here)
+__device__ __forceinline__ void rgb_half4(uint32_t v, float scale, float bias, uint32_t& lo, uint32_t& hi)
+{
+#pragma clang fp contract(off)
+    uint32_t h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float f = (float)((v >> (8 * k)) & 0xffu) * scale + bias;
+        h[k] = (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    }
+    lo = h[0] | (h[1] << 16);
+    hi = h[2] | (h[3] << 16);
+}
+
+// The unit's bytes, in the job's format, to its place in the frame at `frame`.
+__device__ __forceinline__ void rgb_write(const RgbJob& J, const RgbUnit& t, uint32_t (&c)[3][4], uint8_t* frame)
+{
+    if (J.bgr) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const uint32_t s = c[0][q]; c[0][q] = c[2][q]; c[2][q] = s; }
+    }
+    uint8_t* const row = frame + (int64_t)t.r * J.pitch;
+    if (J.format == H264R_RGB_PACKED_U8) {
+        uint32_t w[12];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                       // 4 pixels: c0 c1 c2 c0 | c1 c2 c0 c1 | c2 c0 c1 c2
+            const uint32_t a = c[0][q], b = c[1][q], d = c[2][q];
+            w[3 * q + 0] = rgb_perm(d, rgb_perm(b, a, 0x01000400u), 0x03040100u);   // a0 b0 d0 a1
+            w[3 * q + 1] = rgb_perm(a, rgb_perm(d, b, 0x02000501u), 0x03060100u);   // b1 d1 a2 b2
+            w[3 * q + 2] = rgb_perm(b, rgb_perm(d, a, 0x07000306u), 0x03070100u);   // d2 a3 b3 d3
+        }
+        rgb_store<12>(row + 3 * t.x, w, 3 * t.n);
+    } else if (J.format == H264R_RGB_PACKED_U8X4) {
+        uint32_t w[16];
+        const uint32_t al = (uint32_t)J.alpha * 0x01010101u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t ab_lo = rgb_perm(c[1][q], c[0][q], 0x05010400u);   // a0 b0 a1 b1
+            const uint32_t ab_hi = rgb_perm(c[1][q], c[0][q], 0x07030602u);   // a2 b2 a3 b3
+            const uint32_t dx_lo = rgb_perm(al, c[2][q], 0x04010400u);        // d0 al d1 al
+            const uint32_t dx_hi = rgb_perm(al, c[2][q], 0x04030402u);        // d2 al d3 al
+            w[4 * q + 0] = rgb_perm(dx_lo, ab_lo, 0x05040100u);
+            w[4 * q + 1] = rgb_perm(dx_lo, ab_lo, 0x07060302u);
+            w[4 * q + 2] = rgb_perm(dx_hi, ab_hi, 0x05040100u);
+            w[4 * q + 3] = rgb_perm(dx_hi, ab_hi, 0x07060302u);
+        }
+        rgb_store<16>(row + 4 * t.x, w, 4 * t.n);
+    } else if (J.format == H264R_RGB_PLANAR_U8) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) rgb_store<4>(row + J.plane_off[p] + t.x, c[p], t.n);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            uint32_t w[8];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) rgb_half4(c[p][q], J.scale[p], J.bias[p], w[2 * q], w[2 * q + 1]);
+            rgb_store<8>(row + J.plane_off[p] + 2 * t.x, w, 2 * t.n);
+        }
+    }
+}
+
+// Unit i of a frame: every load it needs (t.n = 0: there is no such unit).
+template <int MODE>
+__device__ __forceinline__ void rgb_fetch(const RgbJob& J, int kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
+                                          const uint8_t* const (&vp)[2], int i, int total, int upr, RgbUnit& t)
+{
+    t.n = 0;
+    if (i >= total) return;
+    t.r = i / upr;
+    t.x = (i - t.r * upr) * RGB_UNIT;
+    t.n = min(RGB_UNIT, J.lw - t.x);
+    const bool whole = t.n == RGB_UNIT;
+    const uint8_t* const ys = rgb_row(yp[0], yp[1], J.y0 + t.r, J.lpitch, kind);
+    if (!ys) t.y = make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
+    else if (whole) t.y = ld16u(ys + J.x0 + t.x);
+    else t.y = rgb_ld_clamped(ys + J.x0, t.x, J.lw - 1, RGB_UNIT);
+    if (MODE == RGB_MONO) return;
+    // the chroma rows j0 (and j1) of the cropped rectangle, and the unit's first chroma column
+    const int i0 = MODE < RGB_REP ? t.x : t.x >> 1;
+    int ja = t.r, jb = t.r;
+    if (MODE >= RGB_REP && J.sub_h == 2) {
+        ja = t.r >> 1;
+        jb = (t.r & 1) ? min(ja + 1, J.ch - 1) : max(ja - 1, 0);
+    }
+    const uint8_t* const ur = rgb_row(up[0], up[1], J.cy0 + ja, J.cpitch, kind);
+    const uint8_t* const vr = rgb_row(vp[0], vp[1], J.cy0 + ja, J.cpitch, kind);
+    t.ua = rgb_ld_chroma(ur ? ur + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    t.va = rgb_ld_chroma(vr ? vr + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    if (MODE == RGB_BIL2) {
+        const uint8_t* const ub = rgb_row(up[0], up[1], J.cy0 + jb, J.cpitch, kind);
+        const uint8_t* const vb = rgb_row(vp[0], vp[1], J.cy0 + jb, J.cpitch, kind);
+        t.ub = rgb_ld_chroma(ub ? ub + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+        t.vb = rgb_ld_chroma(vb ? vb + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ void rgb_finish(const RgbJob& J, const RgbUnit& t, uint8_t* fdst)
+{
+    if (t.n == 0) return;
+    uint32_t c[3][4];
+    rgb_convert<MODE>(J, t, c);
+    rgb_write(J, t, c, fdst);
+}
+
+// The units of one frame that fall to this thread, RGB_THREADS apart: every load, then convert and store.
+template <int MODE>
+__device__ __forceinline__ void rgb_units(const RgbJob& J, int kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
+                                          const uint8_t* const (&vp)[2], int base, int total, int upr, uint8_t* fdst)
+{
+    static_assert(RGB_ITEMS == 2, "rgb_units names its units");
+    RgbUnit t0, t1;
+    rgb_fetch<MODE>(J, kind, yp, up, vp, base, total, upr, t0);
+    rgb_fetch<MODE>(J, kind, yp, up, vp, base + RGB_THREADS, total, upr, t1);
+    rgb_finish<MODE>(J, t0, fdst);
+    rgb_finish<MODE>(J, t1, fdst);
+}
+
+}  // namespace h264r
+
+extern "C" __global__ void __launch_bounds__(RGB_THREADS)
+k_output_rgb(RgbJob job, const h264r_out_frame* __restrict__ frames, uint8_t* dst, int* err)
+{
+    const RgbJob& J = job;
+    const int upr = rgb_units_per_row(J.lw);
+    const int total = J.lh * upr;
+    const int base = (int)blockIdx.x * (RGB_THREADS * RGB_ITEMS) + (int)threadIdx.x;
+    if ((int)blockIdx.x * (RGB_THREADS * RGB_ITEMS) >= total) return;
+    const int mode = J.mode;
+
+    for (int f = blockIdx.y; f < J.num_frames; f += gridDim.y) {
+        // the refusals: before any pointer of the frame is used
+        const int kind = frames[f].kind;
+        const bool pair = kind == H264R_OUT_FIELD_PAIR;
+        const uint8_t* const yp[2] = {frames[f].y[0], frames[f].y[1]};
+        bool ok = (unsigned)kind <= (unsigned)H264R_OUT_UNPAIRED_BOT && yp[0] && (!pair || yp[1]);
+        const uint8_t* const none[2] = {nullptr, nullptr};
+        if (mode == RGB_MONO) {
+            if (ok) rgb_units<RGB_MONO>(J, kind, yp, none, none, base, total, upr, dst + (int64_t)f * J.frame_stride);
+        } else {
+            const uint8_t* const up[2] = {frames[f].u[0], frames[f].u[1]};
+            const uint8_t* const vp[2] = {frames[f].v[0], frames[f].v[1]};
+            ok = ok && up[0] && vp[0] && (!pair || (up[1] && vp[1]));
+            if (ok) {
+                uint8_t* const fdst = dst + (int64_t)f * J.frame_stride;
+                switch (mode) {
+                case RGB_FULL: rgb_units<RGB_FULL>(J, kind, yp, up, vp, base, total, upr, fdst); break;
+                case RGB_GBR:  rgb_units<RGB_GBR>(J, kind, yp, up, vp, base, total, upr, fdst); break;
+                case RGB_REP:  rgb_units<RGB_REP>(J, kind, yp, up, vp, base, total, upr, fdst); break;
+                case RGB_BIL1: rgb_units<RGB_BIL1>(J, kind, yp, up, vp, base, total, upr, fdst); break;
+                default:       rgb_units<RGB_BIL2>(J, kind, yp, up, vp, base, total, upr, fdst); break;
+                }
+            }
+        }
+        if (!ok && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, DEV_ERR_OUTPUT);
     }
 }

@@ -74,7 +74,7 @@ enum DevErr : int {
     DEV_ERR_MBAFF_REF = 5,
     // MBAFF: what that launch sequence does not decode, k_mbaff.hip (OR-ed by k_mbaff_inter)
     DEV_ERR_MBAFF_REFUSED = 8,
-    // a refused output frame (OR-ed by k_output)
+    // a refused output frame (OR-ed by k_output, k_output_rgb)
     DEV_ERR_OUTPUT = 16,
 };
 
@@ -119,3 +119,5 @@ extern "C" __global__ void k_mbaff_intra(h264r_batch b, int diag, int2 rows, int
 extern "C" __global__ void k_mbaff_deblock(h264r_batch b, int diag, int2 rows, int* err);
 // k_output.hip
 extern "C" __global__ void k_output(h264r::OutJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
+// k_output.hip: RGB frames
+extern "C" __global__ void k_output_rgb(h264r::RgbJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);

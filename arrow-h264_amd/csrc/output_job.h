@@ -1,5 +1,6 @@
 // output_job.h -- what h264r_output_frames (h264r_host.hip) hands k_output (k_output.hip): the planes
-// of one output frame, resolved from an h264r_out_desc by the geometry of include/h264r_output.h.
+// of one output frame, resolved from an h264r_out_desc by the geometry of include/h264r_output.h;
+// and what h264r_output_rgb hands k_output_rgb (the same file).
 #pragma once
 
 #include <stdint.h>
@@ -34,5 +35,37 @@ constexpr int OUT_ITEMS = 4;       // 16-byte chunks per thread
 
 // 16-byte chunks a row of w bytes is cut into at most: its destination may start anywhere inside one
 inline __host__ __device__ int out_chunks_per_row(int w) { return (w + 15) / 16 + 1; }
+
+// What h264r_output_rgb hands k_output_rgb: the geometry of an h264r_rgb_desc resolved for the
+// context's chroma format, and the coefficient row of its matrix (h264r_rgb_coefficients).
+// what a unit of k_output_rgb loads and how it forms C8
+enum RgbMode : int32_t {
+    RGB_MONO = 0,     // 4:0:0: u / v are neither tested nor read, C8 = 1024
+    RGB_FULL = 1,     // SubWidthC 1 (4:4:4): 16 samples of one chroma row, C8 = 8 C under either chroma_up
+    RGB_GBR = 2,      // 4:4:4, H264R_CSC_GBR: the three planes copied
+    RGB_REP = 3,      // SubWidthC 2, replicate: 8 samples of one chroma row
+    RGB_BIL1 = 4,     // 4:2:2 bilinear: 8 + 1 samples of one chroma row
+    RGB_BIL2 = 5,     // 4:2:0 bilinear: 8 + 1 samples of two chroma rows, weights 3 and 1
+};
+
+struct RgbJob {
+    int64_t plane_off[3], pitch;   // inside the output frame, bytes (packed formats: plane_off[0] alone)
+    int64_t frame_stride;
+    int32_t lw, lh, x0, y0;        // the cropped luma rectangle inside the (woven) luma plane
+    int32_t cw, ch, cx0, cy0;      // the cropped chroma rectangle (all zero on 4:0:0)
+    int32_t lpitch, cpitch;        // coded widths of the source planes
+    int32_t sub_h;                 // SubHeightC: 1 or 2
+    int32_t mode;                  // RgbMode
+    int32_t format, bgr, alpha;
+    int32_t cy, crv, cgu, cgv, cbu, yo;
+    float scale[3], bias[3];
+    int32_t num_frames;
+};
+
+constexpr int RGB_THREADS = 256;   // k_output_rgb: threads per workgroup
+constexpr int RGB_ITEMS = 2;       // units per thread
+constexpr int RGB_UNIT = 16;       // pixels per unit: horizontally consecutive, of one output row
+
+inline __host__ __device__ int rgb_units_per_row(int lw) { return (lw + RGB_UNIT - 1) / RGB_UNIT; }
 
 }  // namespace h264r

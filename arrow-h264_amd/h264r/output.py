@@ -214,6 +214,71 @@ OUT_FRAME_DTYPE = np.dtype([("kind", "<i4"), ("pad", "<i4"), ("y", "<u8", (2,)),
 assert OUT_FRAME_DTYPE.itemsize == 56
 
 
+# --------------------------------------------------------------------------------------------
+# RGB frames (include/h264r_output.h, h264r_output_rgb): the enums, the ctypes mirrors, the geometry.
+CSC_BT601, CSC_BT709, CSC_BT2020, CSC_GBR = 0, 1, 2, 3            # h264r_rgb_desc.matrix
+UP_REPLICATE, UP_BILINEAR = 0, 1                                  # h264r_rgb_desc.chroma_up
+RGB_PACKED_U8, RGB_PACKED_U8X4, RGB_PLANAR_U8, RGB_PLANAR_F16 = 0, 1, 2, 3   # h264r_rgb_desc.format
+
+
+class RgbDesc(C.Structure):
+    """h264r_rgb_desc"""
+    _fields_ = [("src", OutDesc), ("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_up", C.c_int32),
+                ("format", C.c_int32), ("bgr", C.c_int32), ("alpha", C.c_int32), ("scale", C.c_float * 3),
+                ("bias", C.c_float * 3)]
+
+
+class RgbGeom(C.Structure):
+    """h264r_rgb_geom"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("plane_off", C.c_int64 * 3),
+                ("plane_pitch", C.c_int64 * 3), ("frame_bytes", C.c_int64)]
+
+
+@dataclass(frozen=True)
+class RgbGeometry:
+    """h264r_rgb_geom: the size and the layout of one RGB frame."""
+    width: int
+    height: int
+    plane_off: tuple[int, int, int]
+    plane_pitch: tuple[int, int, int]
+    frame_bytes: int
+
+
+def rgb_desc(src: OutDesc, matrix: int = CSC_BT709, full_range: bool = False, chroma_up: int = UP_REPLICATE,
+             format: int = RGB_PLANAR_U8, bgr: bool = False, alpha: int = 255, scale=(1 / 255,) * 3,
+             bias=(0,) * 3) -> RgbDesc:
+    """An h264r_rgb_desc over a copy of `src` (an OutDesc: size, crop, frame_mbs_only, pitch_align)."""
+    s = OutDesc.from_buffer_copy(src)
+    return RgbDesc(s, int(matrix), int(full_range), int(chroma_up), int(format), int(bgr), int(alpha),
+                   (C.c_float * 3)(*scale), (C.c_float * 3)(*bias))
+
+
+def rgb_geometry(desc: RgbDesc, chroma_format: int = 1) -> RgbGeometry:
+    """h264r_output_rgb_geometry (host only, no GPU): raises H264RError with the library's status."""
+    from . import _check, lib
+    g = RgbGeom()
+    _check("h264r_output_rgb_geometry", lib().h264r_output_rgb_geometry(chroma_format, C.byref(desc), C.byref(g)))
+    return RgbGeometry(int(g.width), int(g.height), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+
+
+def rgb_view(buf, g: RgbGeometry, format: int):
+    """The frames in `buf` (torch uint8 [n, stride >= frame_bytes]) as pixels: [n, H, W, 3 | 4] uint8
+    (packed), [n, 3, H, W] uint8 or float16 (planar); rows keep their pitch, so the view is strided
+    wherever a pitch_align pads them."""
+    import torch
+    n, stride = buf.shape[0], buf.stride(0)
+    H, W, pitch = g.height, g.width, g.plane_pitch[0]
+    if format in (RGB_PACKED_U8, RGB_PACKED_U8X4):
+        ch = 3 if format == RGB_PACKED_U8 else 4
+        return buf.as_strided((n, H, W, ch), (stride, pitch, ch, 1))
+    if format == RGB_PLANAR_U8:
+        return buf.as_strided((n, 3, H, W), (stride, pitch * H, pitch, 1))
+    if stride % 2 or pitch % 2 or buf.data_ptr() % 2:
+        raise ValueError("rgb_view: float16 frames need an even address, stride and pitch")
+    half = buf[:, :g.frame_bytes].view(torch.float16)
+    return half.as_strided((n, 3, H, W), (stride // 2, pitch * H // 2, pitch // 2, 1))
+
+
 def bind(L) -> None:
     """Declare the prototypes of include/h264r_output.h on the library (h264r.lib())."""
     P, I = C.c_void_p, C.c_int
@@ -221,6 +286,12 @@ def bind(L) -> None:
     L.h264r_output_geometry.restype = I
     L.h264r_output_frames.argtypes = [P, C.POINTER(OutDesc), P, I, P, C.c_int64, P]
     L.h264r_output_frames.restype = I
+    L.h264r_rgb_coefficients.argtypes = [I, I, C.POINTER(C.c_int32)]
+    L.h264r_rgb_coefficients.restype = I
+    L.h264r_output_rgb_geometry.argtypes = [I, C.POINTER(RgbDesc), C.POINTER(RgbGeom)]
+    L.h264r_output_rgb_geometry.restype = I
+    L.h264r_output_rgb.argtypes = [P, C.POINTER(RgbDesc), P, I, P, C.c_int64, P]
+    L.h264r_output_rgb.restype = I
 
 
 @dataclass(frozen=True)
@@ -348,3 +419,33 @@ class DeviceOutput:
         _check("h264r_output_frames", L.h264r_output_frames(self.decoder.handle, C.byref(self.desc), C.c_void_p(tptr), n,
                                                            C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
         return dst
+
+    def rgb(self, table, n: int | None = None, *, matrix: int = CSC_BT709, full_range: bool = False,
+            chroma_up: int = UP_REPLICATE, format: int = RGB_PLANAR_U8, bgr: bool = False, alpha: int = 255,
+            scale=(1 / 255,) * 3, bias=(0,) * 3, dst=None, stream: int | None = None):
+        """h264r_output_rgb on the same frame table: n RGB frames (default: the whole table) of this
+        geometry (planar layout, no fake chroma), as a torch tensor that views the destination:
+        [n, H, W, 3 | 4] uint8 for the packed formats, [n, 3, H, W] uint8 or float16 for the planar ones
+        -- a strided view when pitch_align pads the rows.  dst: a torch uint8 tensor [n, dst_frame_stride]
+        on the device, written in place (for PLANAR_F16 its address and stride must be even), or None =
+        a new one of frame_bytes per frame.  Asynchronous on `stream`, as run()."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("rgb: n is needed with a raw frame table")
+        d = rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias)
+        g = rgb_geometry(d, self.chroma_format)
+        if dst is None:
+            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("rgb: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
+        stride = dst.stride(0)
+        L = self.decoder._L
+        _check("h264r_output_rgb", L.h264r_output_rgb(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n,
+                                                     C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
+        return rgb_view(dst[:n], g, format)

@@ -116,6 +116,119 @@ int h264r_output_geometry(int chroma_format_idc, const h264r_out_desc* desc, h26
 int h264r_output_frames(h264r_ctx* ctx, const h264r_out_desc* desc, const h264r_out_frame* frames /*device*/,
                         int num_frames, uint8_t* dst /*device*/, int64_t dst_frame_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RGB frames: h264r_output_rgb writes, from the same frame table, the colour-converted frames a tensor
+ * consumer reads -- packed or planar 8-bit R'G'B', or planar binary16 scaled and biased per channel.
+ * The reference has no RGB output; what follows is the definition, complete: every byte is an exact
+ * function of the source planes, in integers (and, for binary16, three IEEE operations).
+ *
+ * The source frame.  Exactly the planar frame h264r_output_frames writes for the same `src` with
+ * layout H264R_OUT_PLANAR, pitch_align 0 and, on a 4:0:0 context, fake_chroma 1: luma Y[r][x] over the
+ * cropped luma rectangle lw x lh, chroma Cb[j][i], Cr[j][i] over the cropped chroma rectangle cw x ch
+ * (lw = SubWidthC * cw, lh = SubHeightC * ch); field pairs woven (frame row 2 r is the top field's row
+ * r, row 2 r + 1 the bottom field's, in every plane), the missing rows of an unpaired field 128 in every
+ * plane, 4:0:0 chroma 128 everywhere.  r, x, j, i count from the cropped origin.
+ *
+ * Chroma at luma sample (r, x), in units of 1 / 8: C8, for Cb (Cb8) and for Cr (Cr8) alike.
+ *   H264R_UP_REPLICATE:  C8 = 8 * C[r / SubHeightC][x / SubWidthC]  (integer division).
+ *   H264R_UP_BILINEAR:   C8 = sum over the taps below of wv * wh * C[j][i]; the weights sum to 8.
+ *     This is chroma_sample_loc_type 0: chroma co-sited with the even luma columns, midway between two
+ *     luma rows.  The cropped origin keeps that parity (x0 = SubWidthC * crop_left, y0 = SubHeightC * top).
+ *       horizontal, SubWidthC 2:  x even: i = x / 2, wh = 2.
+ *                                 x odd:  i0 = (x - 1) / 2, i1 = min(i0 + 1, cw - 1), wh = 1 and 1.
+ *       horizontal, SubWidthC 1:  i = x, wh = 2.
+ *       vertical, SubHeightC 2:   r even: j0 = r / 2, wv = 3;  j1 = max(j0 - 1, 0), wv = 1.
+ *                                 r odd:  j0 = (r - 1) / 2, wv = 3;  j1 = min(j0 + 1, ch - 1), wv = 1.
+ *       vertical, SubHeightC 1:   j = r, wv = 4.
+ *     Indices clamp to the CROPPED chroma rectangle: no sample outside the crop has any influence.  The
+ *     interpolation runs over the woven frame and treats it as progressive: the vertical taps of a
+ *     field pair come from the two fields, those of an unpaired field mix the field with the 128 rows.
+ *   4:0:0 context:       C8 = 1024.
+ *
+ * The matrix.  All arithmetic 32-bit signed, >> an arithmetic shift, clip255(v) = min(max(v, 0), 255):
+ *     R = clip255((8 * cy * (Y - yo) + crv * (Cr8 - 1024)                        + 65536) >> 17)
+ *     G = clip255((8 * cy * (Y - yo) + cgu * (Cb8 - 1024) + cgv * (Cr8 - 1024) + 65536) >> 17)
+ *     B = clip255((8 * cy * (Y - yo) + cbu * (Cb8 - 1024)                        + 65536) >> 17)
+ * with (cy, crv, cgu, cgv, cbu) = floor(real * 2^14 + 1/2) of the reals
+ *     255 / ys,  255 * 2 (1 - Kr) / cs,  -255 * 2 Kb (1 - Kb) / (Kg * cs),  -255 * 2 Kr (1 - Kr) / (Kg * cs),
+ *     255 * 2 (1 - Kb) / cs,        Kg = 1 - Kr - Kb,
+ * (ys, cs, yo) = (219, 224, 16) for full_range 0 and (255, 255, 0) for full_range 1 -- the six values
+ * h264r_rgb_coefficients returns, in the order cy, crv, cgu, cgv, cbu, yo:
+ *     BT.601  limited  19077  26149  -6419  -13320  33050  16      full  16384  22970  -5638  -11700  29032  0
+ *     BT.709  limited  19077  29372  -3494   -8731  34610  16      full  16384  25802  -3069   -7670  30402  0
+ *     BT.2020 limited  19077  27503  -3069  -10657  35091  16      full  16384  24160  -2696   -9361  30825  0
+ * Against clip255(floor(x + 1/2)) of the same expression in real numbers the result differs by at most
+ * 1, in fewer than 0.2 % of all (Y, Cb8, Cr8); every accumulator stays below 2^27.
+ * H264R_CSC_GBR (4:4:4 contexts only): G = Y, B = Cb, R = Cr, copied; full_range and chroma_up are ignored.
+ *
+ * Output channels (c0, c1, c2) = (R, G, B), or (B, G, R) with bgr = 1.
+ *
+ * Formats; one output row holds
+ *     H264R_RGB_PACKED_U8    3 lw bytes   c0 c1 c2 of pixel 0, of pixel 1, ...
+ *     H264R_RGB_PACKED_U8X4  4 lw bytes   c0 c1 c2 alpha
+ *     H264R_RGB_PLANAR_U8      lw bytes   in each of the planes c0, c1, c2
+ *     H264R_RGB_PLANAR_F16   2 lw bytes   in each of the planes c0, c1, c2: channel c of a pixel is
+ *                                         half_rn(float(v) * scale[c] + bias[c]) of its 8-bit value v:
+ *                                         one binary32 multiplication, then one binary32 addition (each
+ *                                         rounded to nearest even, NOT fused), then one conversion to
+ *                                         binary16 (to nearest even), stored little-endian
+ * and src.pitch_align applies to every row as in h264r_output_geometry: plane_pitch is the row's bytes
+ * for pitch_align 0 or 1, else those rounded up to a multiple of it.  A packed frame is one plane of lh
+ * rows (plane_off[0] = 0; [1], [2] and their pitches 0); a planar frame three planes of lh rows each,
+ * plane_off[k] = k * plane_pitch[0] * lh; frame_bytes is the sum over the planes of pitch * lh.
+ */
+#define H264R_CSC_BT601   0   /* matrix_coefficients 5 / 6: Kr 0.299,  Kb 0.114  */
+#define H264R_CSC_BT709   1   /* matrix_coefficients 1:     Kr 0.2126, Kb 0.0722 */
+#define H264R_CSC_BT2020  2   /* matrix_coefficients 9:     Kr 0.2627, Kb 0.0593 */
+#define H264R_CSC_GBR     3   /* matrix_coefficients 0: G = Y, B = Cb, R = Cr; 4:4:4 contexts only */
+
+#define H264R_UP_REPLICATE 0  /* the chroma sample of the luma sample's chroma cell */
+#define H264R_UP_BILINEAR  1  /* chroma_sample_loc_type 0 siting, above */
+
+#define H264R_RGB_PACKED_U8    0   /* c0 c1 c2 per pixel, 3 bytes */
+#define H264R_RGB_PACKED_U8X4  1   /* c0 c1 c2 alpha per pixel, 4 bytes */
+#define H264R_RGB_PLANAR_U8    2   /* plane c0, plane c1, plane c2 */
+#define H264R_RGB_PLANAR_F16   3   /* the same planes as IEEE binary16, normalised */
+
+typedef struct h264r_rgb_desc {
+    h264r_out_desc src;        /* size, crop, frame_mbs_only, pitch_align as for h264r_output_frames;
+                                  src.layout and src.fake_chroma must be 0 */
+    int32_t matrix, full_range, chroma_up, format;   /* H264R_CSC_*, 0 / 1, H264R_UP_*, H264R_RGB_* */
+    int32_t bgr;               /* 0: (c0, c1, c2) = (R, G, B); 1: (B, G, R) */
+    int32_t alpha;             /* 0..255, H264R_RGB_PACKED_U8X4 only */
+    float   scale[3], bias[3]; /* H264R_RGB_PLANAR_F16 only, indexed by output channel c0..c2 */
+} h264r_rgb_desc;
+
+typedef struct h264r_rgb_geom {               /* filled by h264r_output_rgb_geometry */
+    int32_t width, height;                    /* the cropped luma rectangle */
+    int64_t plane_off[3], plane_pitch[3];     /* packed formats: [0] only */
+    int64_t frame_bytes;
+} h264r_rgb_geom;
+
+/* Host only.  out = cy, crv, cgu, cgv, cbu, yo of the table above.  H264R_EINVAL: NULL out, a matrix
+ * other than BT601 / BT709 / BT2020 (GBR has no coefficients), full_range not 0 / 1. */
+int h264r_rgb_coefficients(int matrix, int full_range, int32_t out[6]);
+
+/* Host only, no GPU needed.  H264R_EINVAL: what h264r_output_geometry refuses for desc->src, a
+ * src.layout or src.fake_chroma other than 0, matrix / chroma_up / format out of range, full_range or
+ * bgr not 0 / 1, alpha outside 0..255, a scale or bias that is not finite, a NULL argument.
+ * H264R_EUNSUPPORTED: H264R_CSC_GBR with chroma_format_idc != 3. */
+int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc, h264r_rgb_geom* geom);
+
+/* h264r_output_frames for RGB: the same frame table and kinds, one launch per job, asynchronous on
+ * `stream` under the same stream rules, num_frames == 0 is H264R_OK.  Frame i goes to dst + i *
+ * dst_frame_stride (bytes).  Only the bytes of the frames are written (no pitch padding, nothing between
+ * frame_bytes and dst_frame_stride), and no byte outside a source plane is read.  dst may have any
+ * alignment (PLANAR_F16: a multiple of 2, and so dst_frame_stride); a run of 16 pixels whose destination
+ * is 16-byte aligned is written with 16-byte stores.
+ * H264R_EINVAL / H264R_EUNSUPPORTED as h264r_output_rgb_geometry for the context's chroma format, and
+ * H264R_EINVAL for NULL ctx / frames / dst, num_frames < 0, dst_frame_stride < frame_bytes.
+ * The frame table's mistakes are found on the device exactly as for h264r_output_frames: a kind outside
+ * 0..3 or a NULL plane the kind needs is tested before anything is dereferenced, that frame is skipped,
+ * the error word is set (h264r_check: H264R_EDEVICE) and the other frames are written. */
+int h264r_output_rgb(h264r_ctx* ctx, const h264r_rgb_desc* desc, const h264r_out_frame* frames /*device*/,
+                     int num_frames, void* dst /*device*/, int64_t dst_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
