@@ -1260,6 +1260,120 @@ int h264r_output_rgb(h264r_ctx* c, const h264r_rgb_desc* desc, const h264r_out_f
     return H264R_OK;
 }
 
+// ------------------------------------------------------------- scaled RGB frames (h264r_output.h)
+static int64_t gcd64(int64_t a, int64_t b)
+{
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    return a;
+}
+
+// The layout of one scaled frame and the job the k_output_rgb_scaled kernels take.  Argument errors come before
+// what is merely unsupported, as in rgb_plan.
+static int scale_plan(int fmt, const h264r_scale_desc* d, h264r_rgb_geom* g, h264r::ScaleJob* job)
+{
+    if (!d) return H264R_EINVAL;
+    h264r_rgb_geom full;
+    h264r::RgbJob R;
+    const int st = rgb_plan(fmt, &d->rgb, &full, &R);
+    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
+    if (d->roi_x < 0 || d->roi_y < 0 || d->roi_w < 0 || d->roi_h < 0 || (d->roi_w == 0) != (d->roi_h == 0) ||
+        d->out_w < 1 || d->out_w > H264R_SCALE_MAX_OUT || d->out_h < 1 || d->out_h > H264R_SCALE_MAX_OUT ||
+        (d->filter != H264R_SCALE_BILINEAR && d->filter != H264R_SCALE_AREA) || d->pad != 0)
+        return H264R_EINVAL;
+    if (st != H264R_OK) {
+        // rgb_plan stops at GBR off 4:4:4 before it knows the size: take the size from the source alone
+        h264r_out_geom og;
+        if (output_plan(fmt, &d->rgb.src, &og, nullptr) != H264R_OK) return H264R_EINVAL;
+        full.width = og.luma[2]; full.height = og.luma[3];
+    }
+    const int64_t sw = d->roi_w ? d->roi_w : full.width, sh = d->roi_h ? d->roi_h : full.height;
+    if (d->roi_x + sw > full.width || d->roi_y + sh > full.height) return H264R_EINVAL;
+    if (st != H264R_OK) return st;
+    const int64_t gw = gcd64(sw, d->out_w), gh = gcd64(sh, d->out_h);
+    const int64_t rw = sw / gw, rh = sh / gh;
+    if (d->filter == H264R_SCALE_AREA && rw * rh > h264r::SCALE_AREA_MAX_T) return H264R_EUNSUPPORTED;
+
+    const int format = d->rgb.format;
+    const bool planar = format == H264R_RGB_PLANAR_U8 || format == H264R_RGB_PLANAR_F16;
+    const int64_t bpp = format == H264R_RGB_PACKED_U8 ? 3 : format == H264R_RGB_PACKED_U8X4 ? 4 : format == H264R_RGB_PLANAR_F16 ? 2 : 1;
+    const int64_t pa = d->rgb.src.pitch_align;
+    const int64_t pitch = pa > 1 ? (bpp * d->out_w + pa - 1) / pa * pa : bpp * d->out_w;
+    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * d->out_h;
+    if (g) {
+        *g = h264r_rgb_geom{};
+        g->width = d->out_w; g->height = d->out_h;
+        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * d->out_h; g->plane_pitch[k] = pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) {
+        h264r::ScaleJob J{};
+        J.rgb = R;
+        for (int k = 0; k < 3; ++k) J.rgb.plane_off[k] = planar ? k * pitch * d->out_h : 0;
+        J.rgb.pitch = pitch;
+        J.rgb.frame_stride = frame_bytes;
+        auto axis = [](int64_t S, int64_t D, int64_t gc) {
+            h264r::ScaleAxis a;
+            a.S = (int32_t)S; a.D = (int32_t)D; a.s = (int32_t)(S / gc); a.d = (int32_t)(D / gc);
+            a.inv_d = 1.0f / (float)a.d; a.inv_2D = 1.0f / (float)(2 * a.D);
+            return a;
+        };
+        J.ax = axis(sw, d->out_w, gw);
+        J.ay = axis(sh, d->out_h, gh);
+        J.roi_x = d->roi_x; J.roi_y = d->roi_y;
+        J.filter = d->filter;
+        // the widest window of columns: floor(d s / D) .. ceil((d + 1) s / D) holds ceil(s / D) + 1 at most
+        // (bilinear: 2), and one more in front where the unit starts on the even column before it
+        const int64_t span = (d->filter == H264R_SCALE_AREA ? (J.ax.s + J.ax.d - 1) / J.ax.d + 1 : 2) + (R.mode >= h264r::RGB_REP ? 1 : 0);
+        J.taps = (int32_t)std::min<int64_t>(span, h264r::RGB_UNIT);
+        J.T = (uint32_t)(rw * rh);
+        J.inv_2T = 1.0f / (2.0f * (float)J.T);
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+int h264r_output_rgb_scaled_geometry(int chroma_format_idc, const h264r_scale_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return scale_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h264r_out_frame* frames, int num_frames,
+                            void* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::ScaleJob job;
+    const int st = scale_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (dst_frame_stride < job.rgb.frame_stride) return H264R_EINVAL;
+    if (job.rgb.format == H264R_RGB_PLANAR_F16 && ((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1))
+        return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.rgb.frame_stride = dst_frame_stride;
+    job.rgb.num_frames = num_frames;
+    (void)hipSetDevice(c->device);
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    // ordered after the context's last launch, as h264r_output_frames is
+    if (c->last_stream && c->last_stream != s) {
+        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
+        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
+    }
+    c->last_stream = s;
+    // the kernel of the job's mode and filter; frame z * grid.y + y, so that one launch holds any number
+    using ScaleKernel = void (*)(h264r::ScaleJob, const h264r_out_frame*, uint8_t*, int*);
+    ScaleKernel kernel[h264r::RGB_BIL2 + 1][2] = {};
+#define H264R_SCALE_KERNEL_ENTRY(NAME, MODE, FILTER) kernel[MODE][FILTER] = k_output_rgb_scaled_##NAME;
+    H264R_SCALE_KERNELS(H264R_SCALE_KERNEL_ENTRY)
+#undef H264R_SCALE_KERNEL_ENTRY
+    const int units = job.ay.D * h264r::rgb_units_per_row(job.ax.D);
+    const int gy = std::min(num_frames, 65535);
+    const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
+    hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
+                       static_cast<uint8_t*>(dst), c->d_err);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
 // ------------------------------------------------------------- streaming API
 int h264r_picture_begin(h264r_ctx* c, int w, int h, const h264r_pic* pic, const h264r_slice* slices,
                         const h264r_quant* quant)

@@ -74,7 +74,7 @@ enum DevErr : int {
     DEV_ERR_MBAFF_REF = 5,
     // MBAFF: what that launch sequence does not decode, k_mbaff.hip (OR-ed by k_mbaff_inter)
     DEV_ERR_MBAFF_REFUSED = 8,
-    // a refused output frame (OR-ed by k_output, k_output_rgb)
+    // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled)
     DEV_ERR_OUTPUT = 16,
 };
 
@@ -121,3 +121,20 @@ extern "C" __global__ void k_mbaff_deblock(h264r_batch b, int diag, int2 rows, i
 extern "C" __global__ void k_output(h264r::OutJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
 // k_output.hip: RGB frames
 extern "C" __global__ void k_output_rgb(h264r::RgbJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
+// k_output_scale.hip: scaled RGB frames, one kernel k_output_rgb_scaled_<name> per RgbMode and filter
+#define H264R_SCALE_KERNELS(X)                                 \
+    X(mono_bilinear, h264r::RGB_MONO, H264R_SCALE_BILINEAR)    \
+    X(full_bilinear, h264r::RGB_FULL, H264R_SCALE_BILINEAR)    \
+    X(gbr_bilinear, h264r::RGB_GBR, H264R_SCALE_BILINEAR)      \
+    X(rep_bilinear, h264r::RGB_REP, H264R_SCALE_BILINEAR)      \
+    X(bil1_bilinear, h264r::RGB_BIL1, H264R_SCALE_BILINEAR)    \
+    X(bil2_bilinear, h264r::RGB_BIL2, H264R_SCALE_BILINEAR)    \
+    X(mono_area, h264r::RGB_MONO, H264R_SCALE_AREA)            \
+    X(full_area, h264r::RGB_FULL, H264R_SCALE_AREA)            \
+    X(gbr_area, h264r::RGB_GBR, H264R_SCALE_AREA)              \
+    X(rep_area, h264r::RGB_REP, H264R_SCALE_AREA)              \
+    X(bil1_area, h264r::RGB_BIL1, H264R_SCALE_AREA)            \
+    X(bil2_area, h264r::RGB_BIL2, H264R_SCALE_AREA)
+#define H264R_SCALE_KERNEL_DECL(NAME, MODE, FILTER) \
+    extern "C" __global__ void k_output_rgb_scaled_##NAME(h264r::ScaleJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
+H264R_SCALE_KERNELS(H264R_SCALE_KERNEL_DECL)

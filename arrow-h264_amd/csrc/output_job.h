@@ -1,6 +1,7 @@
 // output_job.h -- what h264r_output_frames (h264r_host.hip) hands k_output (k_output.hip): the planes
 // of one output frame, resolved from an h264r_out_desc by the geometry of include/h264r_output.h;
-// and what h264r_output_rgb hands k_output_rgb (the same file).
+// what h264r_output_rgb hands k_output_rgb (the same file); and what h264r_output_rgb_scaled hands
+// k_output_rgb_scaled (k_output_scale.hip).
 #pragma once
 
 #include <stdint.h>
@@ -67,5 +68,29 @@ constexpr int RGB_ITEMS = 2;       // units per thread
 constexpr int RGB_UNIT = 16;       // pixels per unit: horizontally consecutive, of one output row
 
 inline __host__ __device__ int rgb_units_per_row(int lw) { return (lw + RGB_UNIT - 1) / RGB_UNIT; }
+
+// What h264r_output_rgb_scaled hands k_output_rgb_scaled (k_output_scale.hip): the RgbJob of its
+// h264r_rgb_desc, whose source side (lw .. mode, the coefficients) is that of the full-size RGB frame
+// and whose output side (plane_off, pitch, frame_stride) is the SCALED frame's; the region of interest
+// and, per axis, the sizes the header's formulas take.
+struct ScaleAxis {
+    int32_t S, D;              // source (region of interest) and output size
+    int32_t s, d;              // the same divided by their greatest common divisor (H264R_SCALE_AREA's unit)
+    float inv_d, inv_2D;       // 1 / d and 1 / (2 D): first guesses of scale_div's quotients
+};
+
+struct ScaleJob {
+    RgbJob rgb;
+    ScaleAxis ax, ay;          // columns, rows
+    int32_t roi_x, roi_y;      // the region's origin inside the cropped rectangle
+    int32_t filter;            // H264R_SCALE_*
+    int32_t taps;              // columns of a 16-pixel source unit any output can weigh: 1..16
+    uint32_t T;                // AREA: ax.s * ay.s <= 2^23
+    float inv_2T;
+};
+
+constexpr int SCALE_THREADS = 256; // k_output_rgb_scaled: threads per workgroup = output pixels = 16 units of RGB_UNIT
+constexpr int SCALE_UNITS = SCALE_THREADS / RGB_UNIT;
+constexpr int64_t SCALE_AREA_MAX_T = 1 << 23;
 
 }  // namespace h264r

@@ -279,6 +279,33 @@ def rgb_view(buf, g: RgbGeometry, format: int):
     return half.as_strided((n, 3, H, W), (stride // 2, pitch * H // 2, pitch // 2, 1))
 
 
+# --------------------------------------------------------------------------------------------
+# Scaled RGB frames (include/h264r_output.h, h264r_output_rgb_scaled).
+SCALE_BILINEAR, SCALE_AREA = 0, 1                                 # h264r_scale_desc.filter
+
+
+class ScaleDesc(C.Structure):
+    """h264r_scale_desc"""
+    _fields_ = [("rgb", RgbDesc), ("roi_x", C.c_int32), ("roi_y", C.c_int32), ("roi_w", C.c_int32), ("roi_h", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("filter", C.c_int32), ("pad", C.c_int32)]
+
+
+def scale_desc(rgb: RgbDesc, out_w: int, out_h: int, roi=None, filter: int = SCALE_AREA) -> ScaleDesc:
+    """An h264r_scale_desc over a copy of `rgb`; roi = (x, y, w, h) in luma samples of the cropped
+    rectangle, None = all of it."""
+    x, y, w, h = (0, 0, 0, 0) if roi is None else roi
+    return ScaleDesc(RgbDesc.from_buffer_copy(rgb), int(x), int(y), int(w), int(h), int(out_w), int(out_h), int(filter), 0)
+
+
+def scaled_geometry(desc: ScaleDesc, chroma_format: int = 1) -> RgbGeometry:
+    """h264r_output_rgb_scaled_geometry (host only, no GPU): raises H264RError with the library's status."""
+    from . import _check, lib
+    g = RgbGeom()
+    _check("h264r_output_rgb_scaled_geometry",
+           lib().h264r_output_rgb_scaled_geometry(chroma_format, C.byref(desc), C.byref(g)))
+    return RgbGeometry(int(g.width), int(g.height), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+
+
 def bind(L) -> None:
     """Declare the prototypes of include/h264r_output.h on the library (h264r.lib())."""
     P, I = C.c_void_p, C.c_int
@@ -292,6 +319,10 @@ def bind(L) -> None:
     L.h264r_output_rgb_geometry.restype = I
     L.h264r_output_rgb.argtypes = [P, C.POINTER(RgbDesc), P, I, P, C.c_int64, P]
     L.h264r_output_rgb.restype = I
+    L.h264r_output_rgb_scaled_geometry.argtypes = [I, C.POINTER(ScaleDesc), C.POINTER(RgbGeom)]
+    L.h264r_output_rgb_scaled_geometry.restype = I
+    L.h264r_output_rgb_scaled.argtypes = [P, C.POINTER(ScaleDesc), P, I, P, C.c_int64, P]
+    L.h264r_output_rgb_scaled.restype = I
 
 
 @dataclass(frozen=True)
@@ -448,4 +479,36 @@ class DeviceOutput:
         L = self.decoder._L
         _check("h264r_output_rgb", L.h264r_output_rgb(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n,
                                                      C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
+        return rgb_view(dst[:n], g, format)
+
+    def rgb_scaled(self, table, out_w: int, out_h: int, n: int | None = None, *, roi=None, filter: int = SCALE_AREA,
+                   matrix: int = CSC_BT709, full_range: bool = False, chroma_up: int = UP_REPLICATE,
+                   format: int = RGB_PLANAR_U8, bgr: bool = False, alpha: int = 255, scale=(1 / 255,) * 3, bias=(0,) * 3,
+                   dst=None, stream: int | None = None):
+        """h264r_output_rgb_scaled on the same frame table: the region `roi` = (x, y, w, h) of every RGB
+        frame (luma samples of the cropped rectangle; None = all of it) resampled to out_w x out_h by
+        `filter`, without the full-size frames.  The other keywords, dst and the tensor returned are
+        those of rgb(), at the output size: [n, out_h, out_w, 3 | 4] or [n, 3, out_h, out_w]; this
+        geometry's pitch_align pads the output rows."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("rgb_scaled: n is needed with a raw frame table")
+        d = scale_desc(rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias), out_w, out_h,
+                       roi, filter)
+        g = scaled_geometry(d, self.chroma_format)
+        if dst is None:
+            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("rgb_scaled: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
+        stride = dst.stride(0)
+        L = self.decoder._L
+        _check("h264r_output_rgb_scaled",
+               L.h264r_output_rgb_scaled(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n, C.c_void_p(dst.data_ptr()),
+                                         stride, C.c_void_p(stream or 0)))
         return rgb_view(dst[:n], g, format)

@@ -229,6 +229,83 @@ int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc,
 int h264r_output_rgb(h264r_ctx* ctx, const h264r_rgb_desc* desc, const h264r_out_frame* frames /*device*/,
                      int num_frames, void* dst /*device*/, int64_t dst_frame_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scaled RGB frames: h264r_output_rgb_scaled writes a region of interest of the RGB frame above,
+ * resampled to out_w x out_h, without the full-size frame ever existing.  The reference has no scaler;
+ * what follows is the definition, complete and in integers, by composition with the RGB definition.
+ *
+ * The source.  The three channel planes c0, c1, c2 (8 bits, lh x lw) that h264r_output_rgb defines for
+ * the same h264r_rgb_desc `rgb` and frame-table entry: crop and weave, the 128 rows of an unpaired field,
+ * 4:0:0 chroma, chroma_up (its taps clamp to the CROP, never to the region of interest), matrix, range,
+ * bgr, and H264R_CSC_GBR on 4:4:4.  Every source sample is converted and clipped to 8 bits first; the
+ * resampling below sees nothing but those planes.
+ *
+ * The region of interest.  roi_x, roi_y, roi_w, roi_h in luma samples of the cropped rectangle:
+ * columns roi_x .. roi_x + roi_w - 1, rows roi_y .. roi_y + roi_h - 1.  roi_w == roi_h == 0 stands for
+ * roi_w = lw, roi_h = lh (roi_x and roi_y are then 0, or the region reaches outside).  Call it S_h rows
+ * by S_w columns; sample [i] below counts from its origin.
+ *
+ * The result.  Each channel on its own is resampled to D_h = out_h rows by D_w = out_w columns of
+ * 8-bit values v, and the four formats of h264r_output_rgb apply to v: PACKED_U8, PACKED_U8X4 and
+ * PLANAR_U8 store v (alpha as there), PLANAR_F16 stores half_rn(float(v) * scale[c] + bias[c]) -- the
+ * same three operations, not fused.  rgb.src.pitch_align pads the OUTPUT rows; plane_off, plane_pitch
+ * and frame_bytes are those of h264r_output_rgb_geometry with (out_w, out_h) in place of (lw, lh).
+ *
+ * Per axis, for the output index d, the source size S and the output size D (all divisions are integer
+ * divisions of non-negative numbers):
+ *
+ *   H264R_SCALE_BILINEAR, half-sample centres:
+ *       p  = clamp((2 d + 1) * S - D, 0, 2 D * (S - 1)),   i0 = p / (2 D),   f = p - 2 D * i0,
+ *       w1 = (256 * f + D) / (2 D)   (0..256),   w0 = 256 - w1,   i1 = min(i0 + 1, S - 1).
+ *     With (i0, i1, w0, w1) of the row index as (r0, r1, wv0, wv1) and of the column index as
+ *     (x0, x1, wh0, wh1):
+ *       v = (wv0 * (wh0 * c[r0][x0] + wh1 * c[r0][x1]) + wv1 * (wh0 * c[r1][x0] + wh1 * c[r1][x1]) + 32768) >> 16.
+ *     The sum stays below 2^24 and every intermediate fits 32 bits for S, D <= 16384.  D == S is the
+ *     identity (f = 0 everywhere).
+ *
+ *   H264R_SCALE_AREA, exact box coverage: source sample i weighs
+ *       o_i = max(0, min((d + 1) * S, (i + 1) * D) - max(d * S, i * D)),   sum over i of o_i = S.
+ *     With ov of the row index and oh of the column index:
+ *       A = sum over r, x of ov_r * oh_x * c[r][x],   T = S_h * S_w,   v = (2 A + T) / (2 T):
+ *     round-half-up of the exact coverage-weighted mean.  The value does not depend on the unit: S and D
+ *     of an axis may both be divided by their greatest common divisor.  With rw = S_w / gcd(S_w, D_w) and
+ *     rh = S_h / gcd(S_h, D_h), rw * rh <= 2^23 keeps 2 A + T below 2^32 in that unit; a job beyond that is
+ *     refused with H264R_EUNSUPPORTED.  D == S is the identity; D > S on an axis is allowed and means
+ *     what the formula says (each output takes the one or two samples its interval touches).
+ */
+#define H264R_SCALE_BILINEAR 0
+#define H264R_SCALE_AREA     1
+
+#define H264R_SCALE_MAX_OUT  16384   /* out_w, out_h */
+
+typedef struct h264r_scale_desc {
+    h264r_rgb_desc rgb;                 /* everything of h264r_output_rgb; rgb.src.pitch_align pads the OUTPUT rows */
+    int32_t roi_x, roi_y, roi_w, roi_h; /* luma samples inside the cropped rectangle; w == h == 0: all of it */
+    int32_t out_w, out_h;               /* 1..16384 */
+    int32_t filter;                     /* H264R_SCALE_* */
+    int32_t pad;                        /* 0 */
+} h264r_scale_desc;
+
+/* Host only, no GPU needed.  geom->width, height = out_w, out_h; the layout as above.
+ * H264R_EINVAL: whatever h264r_output_rgb_geometry refuses for desc->rgb; a negative roi_x / roi_y /
+ * roi_w / roi_h, exactly one of roi_w and roi_h zero, a region that reaches outside the cropped
+ * rectangle; out_w or out_h outside 1..16384; a filter other than the two above; a non-zero pad; a NULL
+ * argument.  H264R_EUNSUPPORTED (when nothing above applies): H264R_CSC_GBR with chroma_format_idc != 3,
+ * H264R_SCALE_AREA with rw * rh > 2^23. */
+int h264r_output_rgb_scaled_geometry(int chroma_format_idc, const h264r_scale_desc* desc, h264r_rgb_geom* geom);
+
+/* h264r_output_rgb, scaled: the same frame table and the same four kinds, one launch per job,
+ * asynchronous on `stream` under the same stream rules, num_frames == 0 is H264R_OK.  Frame i goes to
+ * dst + i * dst_frame_stride.  Only the bytes of the frames are written, no byte outside a source plane
+ * is read -- and none outside the crop: the region's samples and the chroma taps they name are all.
+ * dst may have any alignment (PLANAR_F16: a multiple of 2, and so dst_frame_stride).
+ * H264R_EINVAL / H264R_EUNSUPPORTED as h264r_output_rgb_scaled_geometry for the context's chroma format,
+ * and H264R_EINVAL for NULL ctx / frames / dst, num_frames < 0, dst_frame_stride < frame_bytes.
+ * A bad kind or a NULL plane is refused on the device as for h264r_output_rgb: that frame is skipped,
+ * the error word is set (h264r_check: H264R_EDEVICE) and the other frames are written. */
+int h264r_output_rgb_scaled(h264r_ctx* ctx, const h264r_scale_desc* desc, const h264r_out_frame* frames /*device*/,
+                            int num_frames, void* dst /*device*/, int64_t dst_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
