@@ -1120,6 +1120,20 @@ static int output_plan(int fmt, const h264r_out_desc* d, h264r_out_geom* g, h264
     return H264R_OK;
 }
 
+// The stream an output launch goes to: the caller's, or the context's.  The sources are, as a rule, what
+// the context's last launch wrote: ordered as run_batch orders launches.
+static int output_stream(h264r_ctx* c, void* stream, hipStream_t* s)
+{
+    (void)hipSetDevice(c->device);
+    *s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    if (c->last_stream && c->last_stream != *s) {
+        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
+        HIP_OK(hipStreamWaitEvent(*s, c->ev_last, 0));
+    }
+    c->last_stream = *s;
+    return H264R_OK;
+}
+
 int h264r_output_geometry(int chroma_format_idc, const h264r_out_desc* desc, h264r_out_geom* geom)
 {
     if (!geom) return H264R_EINVAL;
@@ -1137,14 +1151,8 @@ int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_ou
     if (num_frames == 0) return H264R_OK;
     job.frame_stride = dst_frame_stride;
     job.num_frames = num_frames;
-    (void)hipSetDevice(c->device);
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-    // the sources are, as a rule, what the context's last launch wrote: ordered as run_batch orders launches
-    if (c->last_stream && c->last_stream != s) {
-        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
-        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
-    }
-    c->last_stream = s;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
     int items = 0;
     for (int k = 0; k < job.nplanes; ++k)
         items = std::max(items, job.pl[k].h * h264r::out_chunks_per_row(job.pl[k].w));
@@ -1170,13 +1178,45 @@ int h264r_rgb_coefficients(int matrix, int full_range, int32_t out[6])
     return H264R_OK;
 }
 
-// The layout of one RGB frame and the job k_output_rgb takes, from the geometry of desc->src.
-static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job)
+// The layout of one RGB frame of w x h pixels: for the caller as an h264r_rgb_geom, and as the output
+// side of the job the RGB kernels take.
+static void rgb_layout(int format, int64_t pa, int64_t w, int64_t h, h264r_rgb_geom* g, h264r::RgbJob* job)
+{
+    const bool planar = format == H264R_RGB_PLANAR_U8 || format == H264R_RGB_PLANAR_F16;
+    const int64_t bpp = format == H264R_RGB_PACKED_U8 ? 3 : format == H264R_RGB_PACKED_U8X4 ? 4 :
+                        format == H264R_RGB_PLANAR_F16 ? 2 : 1;
+    const int64_t pitch = pa > 1 ? (bpp * w + pa - 1) / pa * pa : bpp * w;
+    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * h;
+    if (g) {
+        *g = h264r_rgb_geom{};
+        g->width = (int32_t)w; g->height = (int32_t)h;
+        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * h; g->plane_pitch[k] = pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) {
+        for (int k = 0; k < 3; ++k) job->plane_off[k] = planar ? k * pitch * h : 0;
+        job->pitch = pitch;
+        job->frame_stride = frame_bytes;
+    }
+}
+
+// what both RGB entry points require of dst: room for every frame, and binary16 at even addresses
+static bool rgb_dst_ok(const h264r::RgbJob& job, const void* dst, int64_t dst_frame_stride)
+{
+    if (dst_frame_stride < job.frame_stride) return false;
+    return job.format != H264R_RGB_PLANAR_F16 || !((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1);
+}
+
+// What RGB frames are made from: the descriptor checked, the size of the cropped rectangle of desc->src
+// (known wherever the status is H264R_OK or H264R_EUNSUPPORTED) and the source side of the job: all of
+// it but the layout.
+static int rgb_source(int fmt, const h264r_rgb_desc* d, int32_t size[2], h264r::RgbJob* job)
 {
     if (!d || d->src.layout != H264R_OUT_PLANAR || d->src.fake_chroma != 0) return H264R_EINVAL;
     h264r_out_geom og;
     const int st = output_plan(fmt, &d->src, &og, nullptr);
     if (st != H264R_OK) return st;
+    size[0] = og.luma[2]; size[1] = og.luma[3];
     if (d->matrix < H264R_CSC_BT601 || d->matrix > H264R_CSC_GBR ||
         (d->chroma_up != H264R_UP_REPLICATE && d->chroma_up != H264R_UP_BILINEAR) ||
         d->format < H264R_RGB_PACKED_U8 || d->format > H264R_RGB_PLANAR_F16 ||
@@ -1186,25 +1226,9 @@ static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::
         if (!std::isfinite(d->scale[k]) || !std::isfinite(d->bias[k])) return H264R_EINVAL;
     if (d->matrix == H264R_CSC_GBR && fmt != 3) return H264R_EUNSUPPORTED;
 
-    const int64_t lw = og.luma[2], lh = og.luma[3];
-    const bool planar = d->format == H264R_RGB_PLANAR_U8 || d->format == H264R_RGB_PLANAR_F16;
-    const int64_t bpp = d->format == H264R_RGB_PACKED_U8 ? 3 : d->format == H264R_RGB_PACKED_U8X4 ? 4 :
-                        d->format == H264R_RGB_PLANAR_F16 ? 2 : 1;
-    const int64_t pa = d->src.pitch_align;
-    const int64_t pitch = pa > 1 ? (bpp * lw + pa - 1) / pa * pa : bpp * lw;
-    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * lh;
-    if (g) {
-        *g = h264r_rgb_geom{};
-        g->width = (int32_t)lw; g->height = (int32_t)lh;
-        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * lh; g->plane_pitch[k] = pitch; }
-        g->frame_bytes = frame_bytes;
-    }
     if (job) {
         h264r::RgbJob J{};
-        for (int k = 0; k < 3; ++k) J.plane_off[k] = planar ? k * pitch * lh : 0;
-        J.pitch = pitch;
-        J.frame_stride = frame_bytes;
-        J.lw = (int32_t)lw; J.lh = (int32_t)lh; J.x0 = og.luma[0]; J.y0 = og.luma[1];
+        J.lw = og.luma[2]; J.lh = og.luma[3]; J.x0 = og.luma[0]; J.y0 = og.luma[1];
         J.cx0 = og.chroma[0]; J.cy0 = og.chroma[1]; J.cw = og.chroma[2]; J.ch = og.chroma[3];
         J.lpitch = 16 * d->src.width_mbs;
         J.cpitch = fmt == 3 ? J.lpitch : fmt ? J.lpitch / 2 : 0;
@@ -1224,6 +1248,15 @@ static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::
     return H264R_OK;
 }
 
+// The layout of one RGB frame and the job k_output_rgb takes, from the geometry of desc->src.
+static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job)
+{
+    int32_t size[2];
+    const int st = rgb_source(fmt, d, size, job);
+    if (st == H264R_OK) rgb_layout(d->format, d->src.pitch_align, size[0], size[1], g, job);
+    return st;
+}
+
 int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc, h264r_rgb_geom* geom)
 {
     if (!geom) return H264R_EINVAL;
@@ -1237,20 +1270,12 @@ int h264r_output_rgb(h264r_ctx* c, const h264r_rgb_desc* desc, const h264r_out_f
     h264r::RgbJob job;
     const int st = rgb_plan(c->fmt, desc, nullptr, &job);
     if (st != H264R_OK) return st;
-    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
-    if (job.format == H264R_RGB_PLANAR_F16 && ((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1))
-        return H264R_EINVAL;
+    if (!rgb_dst_ok(job, dst, dst_frame_stride)) return H264R_EINVAL;
     if (num_frames == 0) return H264R_OK;
     job.frame_stride = dst_frame_stride;
     job.num_frames = num_frames;
-    (void)hipSetDevice(c->device);
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-    // ordered after the context's last launch, as h264r_output_frames is
-    if (c->last_stream && c->last_stream != s) {
-        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
-        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
-    }
-    c->last_stream = s;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
     const int units = job.lh * h264r::rgb_units_per_row(job.lw);
     const int per = h264r::RGB_THREADS * h264r::RGB_ITEMS;
     const dim3 grid((unsigned)((units + per - 1) / per), (unsigned)std::min(num_frames, 65535));
@@ -1268,49 +1293,29 @@ static int64_t gcd64(int64_t a, int64_t b)
 }
 
 // The layout of one scaled frame and the job the k_output_rgb_scaled kernels take.  Argument errors come before
-// what is merely unsupported, as in rgb_plan.
+// what is merely unsupported, as in rgb_source.
 static int scale_plan(int fmt, const h264r_scale_desc* d, h264r_rgb_geom* g, h264r::ScaleJob* job)
 {
     if (!d) return H264R_EINVAL;
-    h264r_rgb_geom full;
+    int32_t full[2];                                         // rgb_source knows the size before it finds GBR off 4:4:4
     h264r::RgbJob R;
-    const int st = rgb_plan(fmt, &d->rgb, &full, &R);
+    const int st = rgb_source(fmt, &d->rgb, full, &R);
     if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
     if (d->roi_x < 0 || d->roi_y < 0 || d->roi_w < 0 || d->roi_h < 0 || (d->roi_w == 0) != (d->roi_h == 0) ||
         d->out_w < 1 || d->out_w > H264R_SCALE_MAX_OUT || d->out_h < 1 || d->out_h > H264R_SCALE_MAX_OUT ||
         (d->filter != H264R_SCALE_BILINEAR && d->filter != H264R_SCALE_AREA) || d->pad != 0)
         return H264R_EINVAL;
-    if (st != H264R_OK) {
-        // rgb_plan stops at GBR off 4:4:4 before it knows the size: take the size from the source alone
-        h264r_out_geom og;
-        if (output_plan(fmt, &d->rgb.src, &og, nullptr) != H264R_OK) return H264R_EINVAL;
-        full.width = og.luma[2]; full.height = og.luma[3];
-    }
-    const int64_t sw = d->roi_w ? d->roi_w : full.width, sh = d->roi_h ? d->roi_h : full.height;
-    if (d->roi_x + sw > full.width || d->roi_y + sh > full.height) return H264R_EINVAL;
+    const int64_t sw = d->roi_w ? d->roi_w : full[0], sh = d->roi_h ? d->roi_h : full[1];
+    if (d->roi_x + sw > full[0] || d->roi_y + sh > full[1]) return H264R_EINVAL;
     if (st != H264R_OK) return st;
     const int64_t gw = gcd64(sw, d->out_w), gh = gcd64(sh, d->out_h);
     const int64_t rw = sw / gw, rh = sh / gh;
     if (d->filter == H264R_SCALE_AREA && rw * rh > h264r::SCALE_AREA_MAX_T) return H264R_EUNSUPPORTED;
 
-    const int format = d->rgb.format;
-    const bool planar = format == H264R_RGB_PLANAR_U8 || format == H264R_RGB_PLANAR_F16;
-    const int64_t bpp = format == H264R_RGB_PACKED_U8 ? 3 : format == H264R_RGB_PACKED_U8X4 ? 4 : format == H264R_RGB_PLANAR_F16 ? 2 : 1;
-    const int64_t pa = d->rgb.src.pitch_align;
-    const int64_t pitch = pa > 1 ? (bpp * d->out_w + pa - 1) / pa * pa : bpp * d->out_w;
-    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * d->out_h;
-    if (g) {
-        *g = h264r_rgb_geom{};
-        g->width = d->out_w; g->height = d->out_h;
-        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * d->out_h; g->plane_pitch[k] = pitch; }
-        g->frame_bytes = frame_bytes;
-    }
+    rgb_layout(d->rgb.format, d->rgb.src.pitch_align, d->out_w, d->out_h, g, &R);
     if (job) {
         h264r::ScaleJob J{};
         J.rgb = R;
-        for (int k = 0; k < 3; ++k) J.rgb.plane_off[k] = planar ? k * pitch * d->out_h : 0;
-        J.rgb.pitch = pitch;
-        J.rgb.frame_stride = frame_bytes;
         auto axis = [](int64_t S, int64_t D, int64_t gc) {
             h264r::ScaleAxis a;
             a.S = (int32_t)S; a.D = (int32_t)D; a.s = (int32_t)(S / gc); a.d = (int32_t)(D / gc);
@@ -1345,20 +1350,12 @@ int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h2
     h264r::ScaleJob job;
     const int st = scale_plan(c->fmt, desc, nullptr, &job);
     if (st != H264R_OK) return st;
-    if (dst_frame_stride < job.rgb.frame_stride) return H264R_EINVAL;
-    if (job.rgb.format == H264R_RGB_PLANAR_F16 && ((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1))
-        return H264R_EINVAL;
+    if (!rgb_dst_ok(job.rgb, dst, dst_frame_stride)) return H264R_EINVAL;
     if (num_frames == 0) return H264R_OK;
     job.rgb.frame_stride = dst_frame_stride;
     job.rgb.num_frames = num_frames;
-    (void)hipSetDevice(c->device);
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-    // ordered after the context's last launch, as h264r_output_frames is
-    if (c->last_stream && c->last_stream != s) {
-        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
-        HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
-    }
-    c->last_stream = s;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
     // the kernel of the job's mode and filter; frame z * grid.y + y, so that one launch holds any number
     using ScaleKernel = void (*)(h264r::ScaleJob, const h264r_out_frame*, uint8_t*, int*);
     ScaleKernel kernel[h264r::RGB_BIL2 + 1][2] = {};

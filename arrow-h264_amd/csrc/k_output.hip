@@ -160,47 +160,15 @@ k_output(OutJob job, const h264r_out_frame* __restrict__ frames, uint8_t* dst, i
 namespace h264r {
 
 // The unit's 16 pixels as 16 bytes per channel: c[0] = R, c[1] = G, c[2] = B.
-// TWIN: rgb_pixel (k_output_scale.hip) is this arithmetic for one pixel; a change goes into both.
 template <int MODE>
 __device__ __forceinline__ void rgb_convert(const RgbJob& J, const RgbUnit& t, uint32_t (&c)[3][4])
 {
-    if (MODE == RGB_GBR) {
-        c[0][0] = t.va.x; c[0][1] = t.va.y; c[0][2] = t.va.z; c[0][3] = t.va.w;
-        c[1][0] = t.y.x;  c[1][1] = t.y.y;  c[1][2] = t.y.z;  c[1][3] = t.y.w;
-        c[2][0] = t.ua.x; c[2][1] = t.ua.y; c[2][2] = t.ua.z; c[2][3] = t.ua.w;
-        return;
-    }
-    const int ky = 8 * J.cy;
 #pragma unroll
     for (int q = 0; q < 4; ++q) c[0][q] = c[1][q] = c[2][q] = 0;
 #pragma unroll
     for (int k = 0; k < RGB_UNIT; ++k) {
-        // every factor fits 24 bits and every sum 27: v_mad_i32_i24
-        const int yt = __mul24(ky, rgb_byte(t.y, k) - J.yo) + 65536;
         int r, g, b;
-        if (MODE == RGB_MONO) {
-            r = g = b = rgb_clip255_sh17(yt);
-        } else {
-            int cb8, cr8;
-            if (MODE == RGB_FULL) {
-                cb8 = 8 * rgb_byte(t.ua, k);
-                cr8 = 8 * rgb_byte(t.va, k);
-            } else {
-                const int m = k >> 1, m1 = (MODE != RGB_REP && (k & 1)) ? m + 1 : m;    // wh 2, or 1 and 1
-                const int hu = rgb_byte(t.ua, m) + rgb_byte(t.ua, m1), hv = rgb_byte(t.va, m) + rgb_byte(t.va, m1);
-                if (MODE == RGB_BIL2) {
-                    cb8 = 3 * hu + rgb_byte(t.ub, m) + rgb_byte(t.ub, m1);              // wv 3 and 1
-                    cr8 = 3 * hv + rgb_byte(t.vb, m) + rgb_byte(t.vb, m1);
-                } else {
-                    cb8 = 4 * hu;
-                    cr8 = 4 * hv;
-                }
-            }
-            const int cbd = cb8 - 1024, crd = cr8 - 1024;
-            r = rgb_clip255_sh17(yt + __mul24(J.crv, crd));
-            g = rgb_clip255_sh17(yt + __mul24(J.cgu, cbd) + __mul24(J.cgv, crd));
-            b = rgb_clip255_sh17(yt + __mul24(J.cbu, cbd));
-        }
+        rgb_pixel<MODE>(J, t, k, r, g, b);
         c[0][k >> 2] |= (uint32_t)r << (8 * (k & 3));
         c[1][k >> 2] |= (uint32_t)g << (8 * (k & 3));
         c[2][k >> 2] |= (uint32_t)b << (8 * (k & 3));
@@ -208,7 +176,6 @@ __device__ __forceinline__ void rgb_convert(const RgbJob& J, const RgbUnit& t, u
 }
 
 // Unit i of a frame: every load it needs (t.n = 0: there is no such unit).
-// TWIN: rgb_fetch_at (k_output_scale.hip) loads the same for a unit at any column; a change goes into both.
 template <int MODE>
 __device__ __forceinline__ void rgb_fetch(const RgbJob& J, int kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
                                           const uint8_t* const (&vp)[2], int i, int total, int upr, RgbUnit& t)
@@ -218,29 +185,7 @@ __device__ __forceinline__ void rgb_fetch(const RgbJob& J, int kind, const uint8
     t.r = i / upr;
     t.x = (i - t.r * upr) * RGB_UNIT;
     t.n = min(RGB_UNIT, J.lw - t.x);
-    const bool whole = t.n == RGB_UNIT;
-    const uint8_t* const ys = rgb_row(yp[0], yp[1], J.y0 + t.r, J.lpitch, kind);
-    if (!ys) t.y = make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
-    else if (whole) t.y = ld16u(ys + J.x0 + t.x);
-    else t.y = rgb_ld_clamped(ys + J.x0, t.x, J.lw - 1, RGB_UNIT);
-    if (MODE == RGB_MONO) return;
-    // the chroma rows j0 (and j1) of the cropped rectangle, and the unit's first chroma column
-    const int i0 = MODE < RGB_REP ? t.x : t.x >> 1;
-    int ja = t.r, jb = t.r;
-    if (MODE >= RGB_REP && J.sub_h == 2) {
-        ja = t.r >> 1;
-        jb = (t.r & 1) ? min(ja + 1, J.ch - 1) : max(ja - 1, 0);
-    }
-    const uint8_t* const ur = rgb_row(up[0], up[1], J.cy0 + ja, J.cpitch, kind);
-    const uint8_t* const vr = rgb_row(vp[0], vp[1], J.cy0 + ja, J.cpitch, kind);
-    t.ua = rgb_ld_chroma(ur ? ur + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    t.va = rgb_ld_chroma(vr ? vr + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    if (MODE == RGB_BIL2) {
-        const uint8_t* const ub = rgb_row(up[0], up[1], J.cy0 + jb, J.cpitch, kind);
-        const uint8_t* const vb = rgb_row(vp[0], vp[1], J.cy0 + jb, J.cpitch, kind);
-        t.ub = rgb_ld_chroma(ub ? ub + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-        t.vb = rgb_ld_chroma(vb ? vb + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    }
+    rgb_fetch_at<MODE>(J, RgbSrc{kind}, yp, up, vp, t);
 }
 
 template <int MODE>

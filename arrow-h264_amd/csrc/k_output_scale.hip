@@ -18,7 +18,7 @@
 // moved down in registers (scale_fetch; the samples that come in behind the last column repeat it, and
 // weigh nothing) -- every output row ends in such units, and k_output_rgb's bytewise fetch, one round
 // trip per sample, made the waves that hold them ten times as slow as the others.  Only a crop narrower
-// than 16 is still fetched bytewise (scale_ld_clamped).  So nothing outside the crop is read.  Of the unit's 16 pixels the
+// than 16 is still fetched bytewise (scale_ld_clamped, output_rgb.h).  So nothing outside the crop is read.  Of the unit's 16 pixels the
 // first `taps`, rounded up to a multiple of 4, are converted (job-wide: the widest window any output
 // has, at most 16) and weighed: a pixel outside the lane's own window has weight 0, so the bounds that
 // differ between lanes are predicates, not branches.
@@ -42,129 +42,6 @@
 #include "output_rgb.h"
 
 namespace h264r {
-
-// rgb_ld_clamped's sixteen bytes (output_rgb.h), by a loop instead of sixteen predicated loads whose
-// lane masks would be kept in SGPRs across the rows: from the last sample that exists down to the
-// first, each pushed in at the bottom of 128 bits that start as the repeated last sample.  Narrow crops only.
-__device__ __forceinline__ uint4 scale_ld_clamped(const uint8_t* s, int first, int last, int cnt)
-{
-    const uint8_t* const p = s + first;
-    const int nv = min(cnt, last - first + 1);
-    const uint32_t rep = (uint32_t)ld1(p + nv - 1) * 0x01010101u;
-    uint32_t w0 = rep, w1 = rep, w2 = rep, w3 = rep;
-#pragma unroll 1
-    for (int m = nv - 1; m >= 0; --m) {
-        w3 = (w3 << 8) | (w2 >> 24);
-        w2 = (w2 << 8) | (w1 >> 24);
-        w1 = (w1 << 8) | (w0 >> 24);
-        w0 = (w0 << 8) | (uint32_t)ld1(p + m);
-    }
-    return make_uint4(w0, w1, w2, w3);
-}
-
-// rgb_row (output_rgb.h) with the frame's kind as two integers instead of three lane masks: the parity
-// of the rows of 128 (-1: none) and whether a plane holds every second row.  p1 is p0 unless the frame
-// is a field pair, so the row's parity alone picks the plane.
-struct ScaleKind {
-    int fill_parity, half;
-};
-
-__device__ __forceinline__ ScaleKind scale_kind(int kind)
-{
-    ScaleKind k;
-    k.fill_parity = kind == H264R_OUT_UNPAIRED_TOP ? 1 : kind == H264R_OUT_UNPAIRED_BOT ? 0 : -1;
-    k.half = kind != H264R_OUT_FRAME ? 1 : 0;
-    return k;
-}
-
-__device__ __forceinline__ const uint8_t* scale_row(const uint8_t* p0, const uint8_t* p1, int R, int pitch, ScaleKind kind)
-{
-    if ((R & 1) == kind.fill_parity) return nullptr;
-    return ((R & 1) ? p1 : p0) + (int64_t)(R >> kind.half) * pitch;
-}
-
-// rgb_ld_chroma (output_rgb.h) over scale_ld_clamped
-__device__ __forceinline__ uint4 scale_ld_chroma(const uint8_t* s, int i0, int cw, int mode, bool whole)
-{
-    if (!s) return make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
-    const bool wide = mode < RGB_REP;
-    if (!whole) return scale_ld_clamped(s, i0, cw - 1, wide ? 16 : 9);
-    if (wide) return ld16u(s + i0);
-    const uint2 a = ld8u(s + i0);
-    const uint32_t next = mode >= RGB_BIL1 ? ld1(s + min(i0 + 8, cw - 1)) : 0u;
-    return make_uint4(a.x, a.y, next, 0u);
-}
-
-// Pixel k of the unit: R, G, B by the header's matrix (RGB_GBR: the three samples as they are).  TWIN of
-// rgb_convert (k_output.hip), which does the same for a unit's 16 pixels at once and stays as it was
-// measured: a change to the matrix goes into both.  tests/test_gpu_output_scale.py holds the two
-// together (a scaled frame at D = S is byte for byte the frame of h264r_output_rgb).
-template <int MODE>
-__device__ __forceinline__ void rgb_pixel(const RgbJob& J, const RgbUnit& t, int k, int& r, int& g, int& b)
-{
-    if (MODE == RGB_GBR) {
-        r = rgb_byte(t.va, k); g = rgb_byte(t.y, k); b = rgb_byte(t.ua, k);
-        return;
-    }
-    // every factor fits 24 bits and every sum 27: v_mad_i32_i24
-    const int yt = __mul24(8 * J.cy, rgb_byte(t.y, k) - J.yo) + 65536;
-    if (MODE == RGB_MONO) {
-        r = g = b = rgb_clip255_sh17(yt);
-        return;
-    }
-    int cb8, cr8;
-    if (MODE == RGB_FULL) {
-        cb8 = 8 * rgb_byte(t.ua, k);
-        cr8 = 8 * rgb_byte(t.va, k);
-    } else {
-        const int m = k >> 1, m1 = (MODE != RGB_REP && (k & 1)) ? m + 1 : m;    // wh 2, or 1 and 1
-        const int hu = rgb_byte(t.ua, m) + rgb_byte(t.ua, m1), hv = rgb_byte(t.va, m) + rgb_byte(t.va, m1);
-        if (MODE == RGB_BIL2) {
-            cb8 = 3 * hu + rgb_byte(t.ub, m) + rgb_byte(t.ub, m1);              // wv 3 and 1
-            cr8 = 3 * hv + rgb_byte(t.vb, m) + rgb_byte(t.vb, m1);
-        } else {
-            cb8 = 4 * hu;
-            cr8 = 4 * hv;
-        }
-    }
-    const int cbd = cb8 - 1024, crd = cr8 - 1024;
-    r = rgb_clip255_sh17(yt + __mul24(J.crv, crd));
-    g = rgb_clip255_sh17(yt + __mul24(J.cgu, cbd) + __mul24(J.cgv, crd));
-    b = rgb_clip255_sh17(yt + __mul24(J.cbu, cbd));
-}
-
-// The unit of RGB_UNIT source pixels of row r of the cropped rectangle from column x on (even where
-// SubWidthC is 2): every load it needs.  The caller has set t.r, t.x and t.n = min(RGB_UNIT, lw - x).
-// TWIN of rgb_fetch (k_output.hip), which finds row and column from a unit index and fetches a narrow
-// crop's samples with predicated loads; a change to what a unit loads goes into both (see rgb_pixel).
-template <int MODE>
-__device__ __forceinline__ void rgb_fetch_at(const RgbJob& J, ScaleKind kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
-                                             const uint8_t* const (&vp)[2], RgbUnit& t)
-{
-    const bool whole = t.n == RGB_UNIT;
-    const uint8_t* const ys = scale_row(yp[0], yp[1], J.y0 + t.r, J.lpitch, kind);
-    if (!ys) t.y = make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
-    else if (whole) t.y = ld16u(ys + J.x0 + t.x);
-    else t.y = scale_ld_clamped(ys + J.x0, t.x, J.lw - 1, RGB_UNIT);
-    if (MODE == RGB_MONO) return;
-    // the chroma rows j0 (and j1) of the cropped rectangle, and the unit's first chroma column
-    const int i0 = MODE < RGB_REP ? t.x : t.x >> 1;
-    int ja = t.r, jb = t.r;
-    if (MODE >= RGB_REP && J.sub_h == 2) {
-        ja = t.r >> 1;
-        jb = (t.r & 1) ? min(ja + 1, J.ch - 1) : max(ja - 1, 0);
-    }
-    const uint8_t* const ur = scale_row(up[0], up[1], J.cy0 + ja, J.cpitch, kind);
-    const uint8_t* const vr = scale_row(vp[0], vp[1], J.cy0 + ja, J.cpitch, kind);
-    t.ua = scale_ld_chroma(ur ? ur + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    t.va = scale_ld_chroma(vr ? vr + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    if (MODE == RGB_BIL2) {
-        const uint8_t* const ub = scale_row(up[0], up[1], J.cy0 + jb, J.cpitch, kind);
-        const uint8_t* const vb = scale_row(vp[0], vp[1], J.cy0 + jb, J.cpitch, kind);
-        t.ub = scale_ld_chroma(ub ? ub + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-        t.vb = scale_ld_chroma(vb ? vb + J.cx0 : nullptr, i0, J.cw, MODE, whole);
-    }
-}
 
 // n / den for a quotient below 2^16: inv = 1 / den in binary32 guesses it to within one
 __device__ __forceinline__ uint32_t scale_div(uint32_t n, uint32_t den, float inv)
@@ -228,22 +105,22 @@ __device__ __forceinline__ uint4 scale_shr8(uint4 v, int sh)
     return scale_shr(make_uint4(v.x, v.y, rep, rep), sh);
 }
 
-// rgb_fetch_at for a unit at any column.  A unit that reaches past the crop's last column is, where
+// rgb_fetch_at (output_rgb.h) for a unit at any column.  A unit that reaches past the crop's last column is, where
 // the crop is 16 wide at least, the crop's LAST whole unit moved down in registers: wide loads of
 // samples inside the crop and a byte shift, instead of the bytewise fetch (one round trip per sample).
 template <int MODE>
-__device__ __forceinline__ void scale_fetch(const RgbJob& J, ScaleKind kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
+__device__ __forceinline__ void scale_fetch(const RgbJob& J, ScaleSrc src, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
                                             const uint8_t* const (&vp)[2], RgbUnit& t)
 {
     if (t.n == RGB_UNIT || J.lw < RGB_UNIT) {
-        rgb_fetch_at<MODE>(J, kind, yp, up, vp, t);
+        rgb_fetch_at<MODE>(J, src, yp, up, vp, t);
         return;
     }
     RgbUnit b;
     b.r = t.r;
     b.x = J.lw - RGB_UNIT;
     b.n = RGB_UNIT;
-    rgb_fetch_at<MODE>(J, kind, yp, up, vp, b);
+    rgb_fetch_at<MODE>(J, src, yp, up, vp, b);
     const int sh = t.x - b.x;                               // 1..15; even where SubWidthC is 2
     t.y = scale_shr(b.y, sh);
     if (MODE == RGB_MONO) return;
@@ -262,7 +139,7 @@ __device__ __forceinline__ void scale_fetch(const RgbJob& J, ScaleKind kind, con
 
 // The three channel sums of output pixel (dy, dx) of one frame.
 template <int MODE, int FILTER>
-__device__ __forceinline__ void scale_pixel(const ScaleJob& S, ScaleKind kind, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
+__device__ __forceinline__ void scale_pixel(const ScaleJob& S, ScaleSrc src, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
                                             const uint8_t* const (&vp)[2], int dy, int dx, uint32_t (&acc)[3])
 {
     const RgbJob& J = S.rgb;
@@ -288,7 +165,7 @@ __device__ __forceinline__ void scale_pixel(const ScaleJob& S, ScaleKind kind, c
         int iy = wy.lo;
         do {
             t.r = S.roi_y + iy;
-            scale_fetch<MODE>(J, kind, yp, up, vp, t);
+            scale_fetch<MODE>(J, src, yp, up, vp, t);
             uint32_t row[3] = {0, 0, 0};
 #pragma unroll
             for (int q = 0; q < RGB_UNIT / 4; ++q) {
@@ -339,7 +216,7 @@ __device__ __forceinline__ void scale_job(const ScaleJob& S, const h264r_out_fra
     const uint8_t* const y0 = frames[f].y[0];
     const uint8_t* const u0 = MODE == RGB_MONO ? nullptr : frames[f].u[0];
     const uint8_t* const v0 = MODE == RGB_MONO ? nullptr : frames[f].v[0];
-    const uint8_t* const yp[2] = {y0, pair ? frames[f].y[1] : y0};                  // see scale_row
+    const uint8_t* const yp[2] = {y0, pair ? frames[f].y[1] : y0};                  // see scale_row (output_rgb.h)
     const uint8_t* const up[2] = {u0, pair && MODE != RGB_MONO ? frames[f].u[1] : u0};
     const uint8_t* const vp[2] = {v0, pair && MODE != RGB_MONO ? frames[f].v[1] : v0};
     bool ok = (unsigned)kind <= (unsigned)H264R_OUT_UNPAIRED_BOT && yp[0] && yp[1];
@@ -384,7 +261,7 @@ __device__ __forceinline__ void scale_job(const ScaleJob& S, const h264r_out_fra
     uint32_t v[3];
     {
         uint32_t acc[3] = {0, 0, 0};
-        scale_pixel<MODE, FILTER>(S, scale_kind(kind), yp, up, vp, dy, dx, acc);
+        scale_pixel<MODE, FILTER>(S, ScaleSrc{scale_kind(kind)}, yp, up, vp, dy, dx, acc);
         const uint32_t T = out[SO_T];
         const float inv_2T = __uint_as_float(out[SO_INV_2T]);
 #pragma unroll

@@ -1,9 +1,10 @@
 // output_rgb.h -- the device code the two RGB kernels share: k_output_rgb (k_output.hip) and
 // the k_output_rgb_scaled kernels (k_output_scale.hip).  The unaligned global loads, the 16-pixel source
-// unit with its row addresses and clamped loads, the clamp of the matrix, and the unit's way out: the
-// format's bytes, interleaved in registers and stored as widely as the destination allows.  Only what
-// both use: each kernel's fetch and convert are in its own file and name their twins there.
-// Everything is inlined; neither kernel's registers depend on the other.
+// unit and its fetch (rgb_fetch_at), the matrix for one pixel (rgb_pixel), and the unit's way out: the
+// format's bytes, interleaved in registers and stored as widely as the destination allows.  There is one
+// fetch and one conversion; what differs between the kernels is how a row's address and a partial
+// unit's samples are obtained, and that is a policy type each kernel hands to the fetch (RgbSrc,
+// ScaleSrc).  Everything is inlined; neither kernel's registers depend on the other.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -76,16 +77,103 @@ __device__ __forceinline__ uint4 rgb_ld_clamped(const uint8_t* s, int first, int
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// rgb_ld_clamped's sixteen bytes, by a loop instead of sixteen predicated loads whose lane masks would
+// be kept in SGPRs across the rows: from the last sample that exists down to the first, each pushed in
+// at the bottom of 128 bits that start as the repeated last sample.  Narrow crops only.
+__device__ __forceinline__ uint4 scale_ld_clamped(const uint8_t* s, int first, int last, int cnt)
+{
+    const uint8_t* const p = s + first;
+    const int nv = min(cnt, last - first + 1);
+    const uint32_t rep = (uint32_t)ld1(p + nv - 1) * 0x01010101u;
+    uint32_t w0 = rep, w1 = rep, w2 = rep, w3 = rep;
+#pragma unroll 1
+    for (int m = nv - 1; m >= 0; --m) {
+        w3 = (w3 << 8) | (w2 >> 24);
+        w2 = (w2 << 8) | (w1 >> 24);
+        w1 = (w1 << 8) | (w0 >> 24);
+        w0 = (w0 << 8) | (uint32_t)ld1(p + m);
+    }
+    return make_uint4(w0, w1, w2, w3);
+}
+
+// rgb_row with the frame's kind as two integers instead of three lane masks: the parity of the rows of
+// 128 (-1: none) and whether a plane holds every second row.  p1 is p0 unless the frame is a field
+// pair, so the row's parity alone picks the plane.
+struct ScaleKind {
+    int fill_parity, half;
+};
+
+__device__ __forceinline__ ScaleKind scale_kind(int kind)
+{
+    ScaleKind k;
+    k.fill_parity = kind == H264R_OUT_UNPAIRED_TOP ? 1 : kind == H264R_OUT_UNPAIRED_BOT ? 0 : -1;
+    k.half = kind != H264R_OUT_FRAME ? 1 : 0;
+    return k;
+}
+
+__device__ __forceinline__ const uint8_t* scale_row(const uint8_t* p0, const uint8_t* p1, int R, int pitch, ScaleKind kind)
+{
+    if ((R & 1) == kind.fill_parity) return nullptr;
+    return ((R & 1) ? p1 : p0) + (int64_t)(R >> kind.half) * pitch;
+}
+
+// Where a unit's samples come from, for rgb_fetch_at: row() is the address of row R of a plane of the
+// woven frame, ld_clamped() a partial unit's samples.  RgbSrc is k_output_rgb's; ScaleSrc the scaled
+// kernels', which have no SGPRs to spare for RgbSrc's lane masks.
+struct RgbSrc {
+    int kind;
+    __device__ __forceinline__ const uint8_t* row(const uint8_t* const (&p)[2], int R, int pitch) const { return rgb_row(p[0], p[1], R, pitch, kind); }
+    static __device__ __forceinline__ uint4 ld_clamped(const uint8_t* s, int first, int last, int cnt) { return rgb_ld_clamped(s, first, last, cnt); }
+};
+
+struct ScaleSrc {
+    ScaleKind kind;
+    __device__ __forceinline__ const uint8_t* row(const uint8_t* const (&p)[2], int R, int pitch) const { return scale_row(p[0], p[1], R, pitch, kind); }
+    static __device__ __forceinline__ uint4 ld_clamped(const uint8_t* s, int first, int last, int cnt) { return scale_ld_clamped(s, first, last, cnt); }
+};
+
 // One chroma row's samples for the unit at chroma column i0: s = the row at the crop's first column.
+template <class SRC>
 __device__ __forceinline__ uint4 rgb_ld_chroma(const uint8_t* s, int i0, int cw, int mode, bool whole)
 {
     if (!s) return make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
     const bool wide = mode < RGB_REP;
-    if (!whole) return rgb_ld_clamped(s, i0, cw - 1, wide ? 16 : 9);
+    if (!whole) return SRC::ld_clamped(s, i0, cw - 1, wide ? 16 : 9);
     if (wide) return ld16u(s + i0);
     const uint2 a = ld8u(s + i0);
     const uint32_t next = mode >= RGB_BIL1 ? ld1(s + min(i0 + 8, cw - 1)) : 0u;
     return make_uint4(a.x, a.y, next, 0u);
+}
+
+// The unit of RGB_UNIT source pixels of row r of the cropped rectangle from column x on (even where
+// SubWidthC is 2): every load it needs.  The caller has set t.r, t.x and t.n = min(RGB_UNIT, lw - x).
+template <int MODE, class SRC>
+__device__ __forceinline__ void rgb_fetch_at(const RgbJob& J, SRC src, const uint8_t* const (&yp)[2], const uint8_t* const (&up)[2],
+                                             const uint8_t* const (&vp)[2], RgbUnit& t)
+{
+    const bool whole = t.n == RGB_UNIT;
+    const uint8_t* const ys = src.row(yp, J.y0 + t.r, J.lpitch);
+    if (!ys) t.y = make_uint4(RGB_GREY, RGB_GREY, RGB_GREY, RGB_GREY);
+    else if (whole) t.y = ld16u(ys + J.x0 + t.x);
+    else t.y = SRC::ld_clamped(ys + J.x0, t.x, J.lw - 1, RGB_UNIT);
+    if (MODE == RGB_MONO) return;
+    // the chroma rows j0 (and j1) of the cropped rectangle, and the unit's first chroma column
+    const int i0 = MODE < RGB_REP ? t.x : t.x >> 1;
+    int ja = t.r, jb = t.r;
+    if (MODE >= RGB_REP && J.sub_h == 2) {
+        ja = t.r >> 1;
+        jb = (t.r & 1) ? min(ja + 1, J.ch - 1) : max(ja - 1, 0);
+    }
+    const uint8_t* const ur = src.row(up, J.cy0 + ja, J.cpitch);
+    const uint8_t* const vr = src.row(vp, J.cy0 + ja, J.cpitch);
+    t.ua = rgb_ld_chroma<SRC>(ur ? ur + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    t.va = rgb_ld_chroma<SRC>(vr ? vr + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    if (MODE == RGB_BIL2) {
+        const uint8_t* const ub = src.row(up, J.cy0 + jb, J.cpitch);
+        const uint8_t* const vb = src.row(vp, J.cy0 + jb, J.cpitch);
+        t.ub = rgb_ld_chroma<SRC>(ub ? ub + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+        t.vb = rgb_ld_chroma<SRC>(vb ? vb + J.cx0 : nullptr, i0, J.cw, MODE, whole);
+    }
 }
 
 __device__ __forceinline__ int rgb_byte(const uint4& v, int k)
@@ -97,6 +185,41 @@ __device__ __forceinline__ int rgb_byte(const uint4& v, int k)
 // clip255(v >> 17), clamped BEFORE the shift: min(max(v, 0), 2^25 - 1) >> 17 is the same number, and it
 // keeps the compiler from fusing shift and clamp of two pixels into gfx950's v_ashr_pk_u8_i32
 __device__ __forceinline__ int rgb_clip255_sh17(int v) { return (int)((uint32_t)min(max(v, 0), (256 << 17) - 1) >> 17); }
+
+// Pixel k of the unit: R, G, B by the header's matrix (RGB_GBR: the three samples as they are).
+template <int MODE>
+__device__ __forceinline__ void rgb_pixel(const RgbJob& J, const RgbUnit& t, int k, int& r, int& g, int& b)
+{
+    if (MODE == RGB_GBR) {
+        r = rgb_byte(t.va, k); g = rgb_byte(t.y, k); b = rgb_byte(t.ua, k);
+        return;
+    }
+    // every factor fits 24 bits and every sum 27: v_mad_i32_i24
+    const int yt = __mul24(8 * J.cy, rgb_byte(t.y, k) - J.yo) + 65536;
+    if (MODE == RGB_MONO) {
+        r = g = b = rgb_clip255_sh17(yt);
+        return;
+    }
+    int cb8, cr8;
+    if (MODE == RGB_FULL) {
+        cb8 = 8 * rgb_byte(t.ua, k);
+        cr8 = 8 * rgb_byte(t.va, k);
+    } else {
+        const int m = k >> 1, m1 = (MODE != RGB_REP && (k & 1)) ? m + 1 : m;    // wh 2, or 1 and 1
+        const int hu = rgb_byte(t.ua, m) + rgb_byte(t.ua, m1), hv = rgb_byte(t.va, m) + rgb_byte(t.va, m1);
+        if (MODE == RGB_BIL2) {
+            cb8 = 3 * hu + rgb_byte(t.ub, m) + rgb_byte(t.ub, m1);              // wv 3 and 1
+            cr8 = 3 * hv + rgb_byte(t.vb, m) + rgb_byte(t.vb, m1);
+        } else {
+            cb8 = 4 * hu;
+            cr8 = 4 * hv;
+        }
+    }
+    const int cbd = cb8 - 1024, crd = cr8 - 1024;
+    r = rgb_clip255_sh17(yt + __mul24(J.crv, crd));
+    g = rgb_clip255_sh17(yt + __mul24(J.cgu, cbd) + __mul24(J.cgv, crd));
+    b = rgb_clip255_sh17(yt + __mul24(J.cbu, cbd));
+}
 
 // bytes s of the eight bytes hi:lo (selector byte values 0..3 = lo's bytes, 4..7 = hi's): v_perm_b32
 __device__ __forceinline__ uint32_t rgb_perm(uint32_t hi, uint32_t lo, uint32_t s) { return __builtin_amdgcn_perm(hi, lo, s); }

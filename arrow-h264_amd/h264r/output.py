@@ -253,12 +253,17 @@ def rgb_desc(src: OutDesc, matrix: int = CSC_BT709, full_range: bool = False, ch
                    (C.c_float * 3)(*scale), (C.c_float * 3)(*bias))
 
 
-def rgb_geometry(desc: RgbDesc, chroma_format: int = 1) -> RgbGeometry:
-    """h264r_output_rgb_geometry (host only, no GPU): raises H264RError with the library's status."""
+def _rgb_geometry(fn: str, desc, chroma_format: int) -> RgbGeometry:
+    """The h264r_rgb_geom that the library's `fn` fills for desc, as an RgbGeometry."""
     from . import _check, lib
     g = RgbGeom()
-    _check("h264r_output_rgb_geometry", lib().h264r_output_rgb_geometry(chroma_format, C.byref(desc), C.byref(g)))
+    _check(fn, getattr(lib(), fn)(chroma_format, C.byref(desc), C.byref(g)))
     return RgbGeometry(int(g.width), int(g.height), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+
+
+def rgb_geometry(desc: RgbDesc, chroma_format: int = 1) -> RgbGeometry:
+    """h264r_output_rgb_geometry (host only, no GPU): raises H264RError with the library's status."""
+    return _rgb_geometry("h264r_output_rgb_geometry", desc, chroma_format)
 
 
 def rgb_view(buf, g: RgbGeometry, format: int):
@@ -299,11 +304,7 @@ def scale_desc(rgb: RgbDesc, out_w: int, out_h: int, roi=None, filter: int = SCA
 
 def scaled_geometry(desc: ScaleDesc, chroma_format: int = 1) -> RgbGeometry:
     """h264r_output_rgb_scaled_geometry (host only, no GPU): raises H264RError with the library's status."""
-    from . import _check, lib
-    g = RgbGeom()
-    _check("h264r_output_rgb_scaled_geometry",
-           lib().h264r_output_rgb_scaled_geometry(chroma_format, C.byref(desc), C.byref(g)))
-    return RgbGeometry(int(g.width), int(g.height), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+    return _rgb_geometry("h264r_output_rgb_scaled_geometry", desc, chroma_format)
 
 
 def bind(L) -> None:
@@ -427,11 +428,10 @@ class DeviceOutput:
         t = torch.from_numpy(tab.view(np.uint8).reshape(-1).copy()).to(device)
         return FrameTable(t, len(rows), keep)
 
-    def run(self, table, n: int | None = None, dst=None, stream: int | None = None):
-        """Write n frames (default: the whole table).  dst: a torch uint8 tensor [n, dst_frame_stride]
-        on the device (written in place: padding and the bytes past frame_bytes keep what they hold) or
-        None = a new [n, frame_bytes] tensor.  Asynchronous on `stream` (a hipStream_t address; None =
-        the context's stream): Decoder.check() before the result is read on another stream."""
+    def _call(self, who: str, fn: str, plan, table, n, dst, stream):
+        """The call path of run, rgb and rgb_scaled: the library's `fn` on the frame table (a FrameTable, or
+        a raw device address with n), the descriptor and the geometry that plan() returns, and dst: checked,
+        or a new tensor of the geometry's frame_bytes per frame.  Returns (dst, n, geometry)."""
         import torch
         from . import _check
         if isinstance(table, FrameTable):
@@ -440,16 +440,22 @@ class DeviceOutput:
         else:
             tptr = self._addr(table)
         if n is None:
-            raise ValueError("run: n is needed with a raw frame table")
+            raise ValueError(f"{who}: n is needed with a raw frame table")
+        d, g = plan()
         if dst is None:
-            dst = torch.empty((n, self.geom.frame_bytes), dtype=torch.uint8, device="cuda")
+            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
         if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
-            raise ValueError("run: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
-        stride = dst.stride(0)
-        L = self.decoder._L
-        _check("h264r_output_frames", L.h264r_output_frames(self.decoder.handle, C.byref(self.desc), C.c_void_p(tptr), n,
-                                                           C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
-        return dst
+            raise ValueError(f"{who}: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
+        _check(fn, getattr(self.decoder._L, fn)(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n,
+                                                C.c_void_p(dst.data_ptr()), dst.stride(0), C.c_void_p(stream or 0)))
+        return dst, n, g
+
+    def run(self, table, n: int | None = None, dst=None, stream: int | None = None):
+        """Write n frames (default: the whole table).  dst: a torch uint8 tensor [n, dst_frame_stride]
+        on the device (written in place: padding and the bytes past frame_bytes keep what they hold) or
+        None = a new [n, frame_bytes] tensor.  Asynchronous on `stream` (a hipStream_t address; None =
+        the context's stream): Decoder.check() before the result is read on another stream."""
+        return self._call("run", "h264r_output_frames", lambda: (self.desc, self.geom), table, n, dst, stream)[0]
 
     def rgb(self, table, n: int | None = None, *, matrix: int = CSC_BT709, full_range: bool = False,
             chroma_up: int = UP_REPLICATE, format: int = RGB_PLANAR_U8, bgr: bool = False, alpha: int = 255,
@@ -460,25 +466,10 @@ class DeviceOutput:
         -- a strided view when pitch_align pads the rows.  dst: a torch uint8 tensor [n, dst_frame_stride]
         on the device, written in place (for PLANAR_F16 its address and stride must be even), or None =
         a new one of frame_bytes per frame.  Asynchronous on `stream`, as run()."""
-        import torch
-        from . import _check
-        if isinstance(table, FrameTable):
-            n = table.n if n is None else n
-            tptr = table.tensor.data_ptr()
-        else:
-            tptr = self._addr(table)
-        if n is None:
-            raise ValueError("rgb: n is needed with a raw frame table")
-        d = rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias)
-        g = rgb_geometry(d, self.chroma_format)
-        if dst is None:
-            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
-        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
-            raise ValueError("rgb: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
-        stride = dst.stride(0)
-        L = self.decoder._L
-        _check("h264r_output_rgb", L.h264r_output_rgb(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n,
-                                                     C.c_void_p(dst.data_ptr()), stride, C.c_void_p(stream or 0)))
+        def plan():
+            d = rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias)
+            return d, rgb_geometry(d, self.chroma_format)
+        dst, n, g = self._call("rgb", "h264r_output_rgb", plan, table, n, dst, stream)
         return rgb_view(dst[:n], g, format)
 
     def rgb_scaled(self, table, out_w: int, out_h: int, n: int | None = None, *, roi=None, filter: int = SCALE_AREA,
@@ -490,25 +481,9 @@ class DeviceOutput:
         `filter`, without the full-size frames.  The other keywords, dst and the tensor returned are
         those of rgb(), at the output size: [n, out_h, out_w, 3 | 4] or [n, 3, out_h, out_w]; this
         geometry's pitch_align pads the output rows."""
-        import torch
-        from . import _check
-        if isinstance(table, FrameTable):
-            n = table.n if n is None else n
-            tptr = table.tensor.data_ptr()
-        else:
-            tptr = self._addr(table)
-        if n is None:
-            raise ValueError("rgb_scaled: n is needed with a raw frame table")
-        d = scale_desc(rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias), out_w, out_h,
-                       roi, filter)
-        g = scaled_geometry(d, self.chroma_format)
-        if dst is None:
-            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
-        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
-            raise ValueError("rgb_scaled: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
-        stride = dst.stride(0)
-        L = self.decoder._L
-        _check("h264r_output_rgb_scaled",
-               L.h264r_output_rgb_scaled(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n, C.c_void_p(dst.data_ptr()),
-                                         stride, C.c_void_p(stream or 0)))
+        def plan():
+            d = scale_desc(rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias), out_w, out_h,
+                           roi, filter)
+            return d, scaled_geometry(d, self.chroma_format)
+        dst, n, g = self._call("rgb_scaled", "h264r_output_rgb_scaled", plan, table, n, dst, stream)
         return rgb_view(dst[:n], g, format)
