@@ -20,6 +20,7 @@
 
 #include "h264r.h"
 #include "h264r_group.h"
+#include "host_ctx.h"
 
 namespace {
 
@@ -106,8 +107,9 @@ struct h264r_group {
     int W = 0, H = 0, max_pics = 0, fmt = 1;   // fmt: chroma_format_idc of the planes
     std::vector<SegDev> give, need;      // peers with rows, increasing rank order
     int give_rows = 0, need_rows = 0;
-    SegDev* d_segs = nullptr;            // give then need
-    uint8_t *d_send = nullptr, *d_recv = nullptr, *h_send = nullptr, *h_recv = nullptr;
+    h264r::DevBuf<SegDev> d_segs;        // give then need
+    h264r::DevBuf<uint8_t> d_send, d_recv;
+    uint8_t *h_send = nullptr, *h_recv = nullptr;
     bool host_pinned = false;
     int64_t sent = 0, received = 0, transfers = 0;
 
@@ -115,14 +117,14 @@ struct h264r_group {
     int64_t rby() const { return 256LL * W; }
     int64_t rbc() const { return fmt == 0 ? 0 : fmt == 1 ? 64LL * W : fmt == 2 ? 128LL * W : 256LL * W; }
     int64_t mbrow() const { return rby() + 2 * rbc(); }
+    h264r_group() = default;
+    h264r_group(const h264r_group&) = delete;
+    h264r_group& operator=(const h264r_group&) = delete;
+    ~h264r_group() { free_buffers(); }
     void free_buffers()
     {
-        if (device >= 0) {
-            (void)hipSetDevice(device);
-            if (d_segs) (void)hipFree(d_segs);
-            if (d_send) (void)hipFree(d_send);
-            if (d_recv) (void)hipFree(d_recv);
-        }
+        if (device >= 0) (void)hipSetDevice(device);
+        d_segs.reset(); d_send.reset(); d_recv.reset();
         if (host_pinned) {
             if (h_send) (void)hipHostFree(h_send);
             if (h_recv) (void)hipHostFree(h_recv);
@@ -130,7 +132,7 @@ struct h264r_group {
             free(h_send);
             free(h_recv);
         }
-        d_segs = nullptr; d_send = d_recv = h_send = h_recv = nullptr;
+        h_send = h_recv = nullptr;
     }
 };
 
@@ -221,7 +223,6 @@ int h264r_group_create_transport(h264r_group** out, int device, int nranks, int 
 int h264r_group_destroy(h264r_group* g)
 {
     if (!g) return H264R_EINVAL;
-    g->free_buffers();
     if (g->comm) rccl().destroy(g->comm);
     delete g;
     return H264R_OK;
@@ -266,15 +267,13 @@ int h264r_group_set_bands_fmt(h264r_group* g, int width_mbs, int height_mbs, int
     const size_t nseg = g->give.size() + g->need.size();
     if (g->device >= 0) {
         (void)hipSetDevice(g->device);
-        if ((nseg && hipMalloc(reinterpret_cast<void**>(&g->d_segs), nseg * sizeof(SegDev)) != hipSuccess) ||
-            (sbytes && hipMalloc(reinterpret_cast<void**>(&g->d_send), sbytes) != hipSuccess) ||
-            (rbytes && hipMalloc(reinterpret_cast<void**>(&g->d_recv), rbytes) != hipSuccess)) {
+        if ((nseg && g->d_segs.reserve(nseg)) || (sbytes && g->d_send.reserve(sbytes)) || (rbytes && g->d_recv.reserve(rbytes))) {
             g->free_buffers();
             return H264R_ENOMEM;
         }
         std::vector<SegDev> all(g->give);
         all.insert(all.end(), g->need.begin(), g->need.end());
-        if (nseg && hipMemcpy(g->d_segs, all.data(), nseg * sizeof(SegDev), hipMemcpyHostToDevice) != hipSuccess) {
+        if (nseg && hipMemcpy(g->d_segs.p, all.data(), nseg * sizeof(SegDev), hipMemcpyHostToDevice) != hipSuccess) {
             g->free_buffers();
             return H264R_EDEVICE;
         }
@@ -350,7 +349,7 @@ int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, u
 
     if (g->device >= 0) {
         (void)hipSetDevice(g->device);
-        if (launch(g->d_segs, g->give.size(), g->d_send, g->give_rows, 0) != hipSuccess) return H264R_EDEVICE;
+        if (launch(g->d_segs.p, g->give.size(), g->d_send.p, g->give_rows, 0) != hipSuccess) return H264R_EDEVICE;
     } else {
         host_copy(g, g->give, nk, g->h_send, pl, stride, false);
     }
@@ -359,16 +358,16 @@ int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, u
         const Rccl& R = rccl();
         bool ok = R.gstart() == ncclSuccess;
         for (const SegDev& sg : g->give)
-            ok = ok && R.send(g->d_send + (size_t)sg.pre * nk * mbrow, (size_t)(sg.r1 - sg.r0) * nk * mbrow, ncclUint8,
+            ok = ok && R.send(g->d_send.p + (size_t)sg.pre * nk * mbrow, (size_t)(sg.r1 - sg.r0) * nk * mbrow, ncclUint8,
                               sg.peer, g->comm, s) == ncclSuccess;
         for (const SegDev& sg : g->need)
-            ok = ok && R.recv(g->d_recv + (size_t)sg.pre * nk * mbrow, (size_t)(sg.r1 - sg.r0) * nk * mbrow, ncclUint8,
+            ok = ok && R.recv(g->d_recv.p + (size_t)sg.pre * nk * mbrow, (size_t)(sg.r1 - sg.r0) * nk * mbrow, ncclUint8,
                               sg.peer, g->comm, s) == ncclSuccess;
         ok = (R.gend() == ncclSuccess) && ok;
         if (!ok) return H264R_EDEVICE;
     } else {
         if (g->device >= 0) {
-            if ((sbytes && hipMemcpyAsync(g->h_send, g->d_send, sbytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            if ((sbytes && hipMemcpyAsync(g->h_send, g->d_send.p, sbytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
                 hipStreamSynchronize(s) != hipSuccess)
                 return H264R_EDEVICE;
         }
@@ -381,12 +380,12 @@ int h264r_group_exchange(h264r_group* g, int num_pics, uint8_t* y, uint8_t* u, u
         ok = (t.finish(t.user) == 0) && ok;
         if (!ok) return H264R_EDEVICE;
         if (g->device >= 0 && rbytes &&
-            hipMemcpyAsync(g->d_recv, g->h_recv, rbytes, hipMemcpyHostToDevice, s) != hipSuccess)
+            hipMemcpyAsync(g->d_recv.p, g->h_recv, rbytes, hipMemcpyHostToDevice, s) != hipSuccess)
             return H264R_EDEVICE;
     }
 
     if (g->device >= 0) {
-        if (launch(g->d_segs + g->give.size(), g->need.size(), g->d_recv, g->need_rows, 1) != hipSuccess)
+        if (launch(g->d_segs.p + g->give.size(), g->need.size(), g->d_recv.p, g->need_rows, 1) != hipSuccess)
             return H264R_EDEVICE;
         if (!g->use_rccl && hipStreamSynchronize(s) != hipSuccess) return H264R_EDEVICE;   // h_recv reused next time
     } else {

@@ -1,4 +1,8 @@
-// h264r_host.hip -- the C ABI of include/h264r.h on top of the gfx950 kernels.
+// h264r_host.hip -- the C ABI of include/h264r.h on top of the gfx950 kernels: contexts, DPB
+// slots, environment knobs, timing, h264r_check, the launch sequences and the two batch entry
+// points.  The streaming API (h264r_picture_begin ...) is host_stream.hip, the output stage
+// (include/h264r_output.h) host_output.hip; host_ctx.h holds what the three share, and
+// picture_stage.h the part of the host layer that needs no device.
 //
 // Host-side replacement of vio::h264::Decoder (decoder.h:301-338):
 //   picture_begin / mb_submit / picture_end   ~ Decoder::init, decode(mb), deblock_filter
@@ -17,7 +21,6 @@
 
 #include <algorithm>
 #include <cerrno>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,177 +29,15 @@
 #include <vector>
 
 #include "h264r.h"
-#include "h264r_output.h"
+#include "host_ctx.h"
 #include "kernels.h"
 #include "wp_math.h"
 
 using namespace h264r;
 
-namespace {
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-        fprintf(stderr, "h264r: %s failed: %s\n", #x, hipGetErrorString(e_)); return H264R_EDEVICE; } } while (0)
-
-const int dequant_coef[6][3] = {{10, 13, 16}, {11, 14, 18}, {13, 16, 20}, {14, 18, 23}, {16, 20, 25}, {18, 23, 29}};
-const int dq8_v[6][6] = {{20, 18, 32, 19, 25, 24}, {22, 19, 35, 21, 28, 26}, {26, 23, 42, 24, 33, 31},
-                         {28, 25, 45, 26, 35, 33}, {32, 28, 51, 30, 40, 38}, {36, 32, 58, 34, 46, 43}};
-
-// normative LevelScale(m, i, j) (transform.cc:93-170 tables dequant_coef / dequant_coef8)
-int norm4(int m, int i, int j)
-{
-    if ((i & 1) == 0 && (j & 1) == 0) return dequant_coef[m][0];
-    if ((i & 1) && (j & 1)) return dequant_coef[m][2];
-    return dequant_coef[m][1];
-}
-int norm8(int m, int i, int j)
-{
-    if (i % 4 == 0 && j % 4 == 0) return dq8_v[m][0];
-    if (i % 2 == 1 && j % 2 == 1) return dq8_v[m][1];
-    if (i % 4 == 2 && j % 4 == 2) return dq8_v[m][2];
-    if ((i % 4 == 0 && j % 2 == 1) || (i % 2 == 1 && j % 4 == 0)) return dq8_v[m][3];
-    if ((i % 4 == 0 && j % 4 == 2) || (i % 4 == 2 && j % 4 == 0)) return dq8_v[m][4];
-    return dq8_v[m][5];
-}
-
-int grid_diag(int step, int W, int H)
-{
-    int ymin = step - (W - 1) > 0 ? (step - (W - 1) + 1) / 2 : 0;
-    int ymax = std::min(step / 2, H - 1);
-    return ymax >= ymin ? ymax - ymin + 1 : 0;
-}
-
-template <typename T>
-int dev_resize(T** p, size_t* cap, size_t n)
-{
-    if (n <= *cap && *p) return H264R_OK;
-    // work still queued may read the old buffer (h264r_picture_end_async): drain it first
-    if (*p) { (void)hipDeviceSynchronize(); (void)hipFree(*p); }
-    *p = nullptr; *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return H264R_ENOMEM;
-    *cap = n;
-    return H264R_OK;
-}
-
-}  // namespace
-
-constexpr int OVERLAP_MAX = 16;     // chunks of the overlapped schedule at most (H264R_OVERLAP)
-
-// Per-batch scratch of one launch sequence.
-struct Scratch {
-    uint8_t* d_dbinfo = nullptr; size_t c_dbinfo = 0;
-    int* d_sync = nullptr; size_t c_sync = 0;      // a sync region (sync_words.h) per chunk of the overlapped schedule
-    int tag = 0;                    // launch-sequence tag (> 0): k_inter4r's SP word
-    // the SP word of each chunk: k_inter4r stores the launch tag there when it met an inter MB of
-    // an SP slice.  Allocated and zeroed once and written by nothing else, so a word only ever
-    // holds tags of earlier launches, whatever their shape
-    int* d_sptag = nullptr;
-    uint8_t* d_hb = nullptr; size_t c_hb = 0;
-    uint32_t epoch = 0;             // tag of the deblocking hand-off records of the last launch
-    uint8_t* d_hb2 = nullptr; size_t c_hb2 = 0;
-    uint32_t epoch2 = 0;            // the same for k_deblock2 (< 2^20: its tags carry the row)
-    uint16_t* d_lvl = nullptr; size_t c_lvl = 0;   // intra dependency level per MB
-    uint32_t* d_list = nullptr; size_t c_list = 0; // intra MBs by level (pic * nmb + addr)
-    int* d_lcnt = nullptr; size_t c_lcnt = 0;      // [count | base | cursor] x LEVEL_IDS
-    uint8_t* d_recon = nullptr; size_t c_recon = 0; // MB-tiled reconstruction, 384 B per (picture, MB)
-    void release()
-    {
-        void* bufs[] = {d_dbinfo, d_sync, d_sptag, d_hb, d_hb2, d_lvl, d_list, d_lcnt, d_recon};
-        for (void* b : bufs) if (b) (void)hipFree(b);
-    }
-};
-
-struct h264r_ctx {
-    int device = 0;
-    int max_w = 0, max_h = 0;
-    int fmt = 1;                          // chroma_format_idc: 1 (4:2:0), 0 (4:0:0) / 2 (4:2:2) (run_422) or 3 (4:4:4, run_444)
-    // 4:4:4: one colour plane's derived batch (k_derive444) -- records, slices, quant, DPB tables --
-    // and the scratch its unused 4:2:0 chroma outputs go to
-    h264r_mb* d444_mbs = nullptr; size_t c444_mbs = 0;
-    h264r_slice* d444_slices = nullptr; size_t c444_slices = 0;
-    h264r_quant* d444_quant = nullptr; size_t c444_quant = 0;
-    const uint8_t** d444_refs = nullptr; size_t c444_refs = 0;
-    uint8_t* d444_chroma = nullptr; size_t c444_chroma = 0;
-    hipStream_t stream = nullptr;
-    // DPB slots
-    uint8_t* slot[H264R_MAX_SLOTS][3] = {};
-    int slot_w[H264R_MAX_SLOTS] = {}, slot_h[H264R_MAX_SLOTS] = {};
-    const uint8_t** d_ref_planes = nullptr;
-    int* d_err = nullptr;                 // [0] device error word (a bounded wait expired), [1] wait bound
-    uint32_t wait_ticks = 0;              // err[1] as last written (s_memrealtime ticks, 100 MHz)
-    uint32_t wait_val = 0;                // its host copy, the source of the async write
-    // streaming-API staging: two pictures, so that one is parsed (h264r_picture_begin /
-    // h264r_mb_submit) while the other is reconstructed (h264r_picture_end_async)
-    struct StreamPic {
-        int pw = 0, ph = 0;
-        std::vector<h264r_mb> h_mbs;
-        std::vector<int16_t> h_levels;
-        std::vector<uint32_t> h_mv;
-        std::vector<int8_t> h_ref;
-        std::vector<h264r_slice> h_slices;
-        h264r_pic h_pic{};
-        h264r_quant h_quant{};
-        h264r_field_poc h_fpoc{};                  // h264r_picture_field_pocs: this picture's record
-        bool has_fpoc = false;
-        std::vector<uint8_t> seen;
-        uint8_t* out = nullptr; size_t c_out = 0;   // pinned planes Y | Cb | Cr, then the error word
-        hipEvent_t done = nullptr;                 // its uploads, launches and readback
-        bool pending = false;
-    };
-    StreamPic sp[2];
-    int sp_fill = 0, sp_wait = 0, sp_pending = 0;
-    bool in_pic = false;
-    // device buffers of the streaming API
-    h264r_mb* d_mbs = nullptr; size_t c_mbs = 0;
-    int16_t* d_levels = nullptr; size_t c_levels = 0;
-    uint32_t* d_mv = nullptr; size_t c_mv = 0;
-    int8_t* d_ref = nullptr; size_t c_ref = 0;
-    h264r_slice* d_slices = nullptr; size_t c_slices = 0;
-    h264r_pic* d_pic = nullptr; size_t c_pic = 0;
-    h264r_quant* d_quant = nullptr; size_t c_quant = 0;
-    h264r_field_poc* d_fpoc = nullptr; size_t c_fpoc = 0;
-    uint8_t* d_out = nullptr; size_t c_out = 0;
-    // per-batch scratch of the launch sequence
-    Scratch sc;
-    int levels_grid = 0;                           // resident workgroups of k_intra_levels
-    int nxcc = 0;                                  // XCDs of the device (k_deblock2's placement)
-    // the per-batch scratch above is reused by every launch: a launch on a stream other
-    // than the previous one first waits for the previous launch (ev_last)
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev_last = nullptr;
-    // the overlapped schedule (launch_all): deblocking of picture chunk k on `side` while the
-    // launch stream reconstructs chunk k + 1; ev_chunk[k] = chunk k reconstructed, ev_side =
-    // the side stream's last deblocking launch (the launch stream waits for it at the end)
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> ev_chunk;
-    hipEvent_t ev_side = nullptr;
-    hipEvent_t ev_fork = nullptr;              // the split deblocking walk: launch stream -> side stream
-    // timing: every kernel of every launch bracketed by events on its stream
-    bool timing = false;
-    int debug = 0;
-    struct Span { int kind; hipEvent_t a, b; };
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    std::vector<Span> spans;
-    int timed_launches = 0;
-};
-
-extern "C" {
-
 int h264r_abi_version(void) { return H264R_ABI_VERSION; }
 
-const char* h264r_strerror(int s)
-{
-    switch (s) {
-    case H264R_OK: return "ok";
-    case H264R_EINVAL: return "invalid argument";
-    case H264R_ENOMEM: return "out of memory";
-    case H264R_EDEVICE: return "HIP runtime error";
-    case H264R_ESTATE: return "call out of order";
-    case H264R_EUNSUPPORTED: return "unsupported configuration";
-    case H264R_ENODEVICE: return "no gfx950 device";
-    default: return "unknown status";
-    }
-}
+const char* h264r_strerror(int s) { return status_string(s); }
 
 int h264r_implicit_w1(int cur_poc, int poc0, int poc1, int long_term0, int long_term1)
 {
@@ -215,37 +56,9 @@ int h264r_device_count(void)
     return ok;
 }
 
-int h264r_quant_init_flat(h264r_quant* q)
-{
-    if (!q) return H264R_EINVAL;
-    for (int t = 0; t < 2; ++t)
-        for (int pl = 0; pl < 3; ++pl)
-            for (int m = 0; m < 6; ++m) {
-                for (int k = 0; k < 16; ++k) q->scale4x4[t][pl][m][k] = (int16_t)(norm4(m, k / 4, k % 4) * 16);
-                for (int k = 0; k < 64; ++k) q->scale8x8[t][pl][m][k] = (int16_t)(norm8(m, k / 8, k % 8) * 16);
-            }
-    return H264R_OK;
-}
+int h264r_quant_init_flat(h264r_quant* q) { return quant_init_flat(q); }
 
-int h264r_quant_init_lists(h264r_quant* q, const int32_t* const qm[12])
-{
-    // Transform::set_quant (transform.cc:259-302): InvLevelScale = dequant_coef x qmatrix.
-    if (!q || !qm) return H264R_EINVAL;
-    for (int i = 0; i < 12; ++i) if (!qm[i]) return H264R_EINVAL;
-    for (int pl = 0; pl < 3; ++pl)
-        for (int m = 0; m < 6; ++m) {
-            for (int k = 0; k < 16; ++k) {
-                q->scale4x4[0][pl][m][k] = (int16_t)(norm4(m, k / 4, k % 4) * qm[pl][k]);
-                q->scale4x4[1][pl][m][k] = (int16_t)(norm4(m, k / 4, k % 4) * qm[3 + pl][k]);
-            }
-            for (int k = 0; k < 64; ++k) {
-                // 8x8 lists: 6 Intra Y, 7 Inter Y, 8 Intra Cb, 9 Inter Cb, 10 Intra Cr, 11 Inter Cr
-                q->scale8x8[0][pl][m][k] = (int16_t)(norm8(m, k / 8, k % 8) * qm[6 + 2 * pl][k]);
-                q->scale8x8[1][pl][m][k] = (int16_t)(norm8(m, k / 8, k % 8) * qm[7 + 2 * pl][k]);
-            }
-        }
-    return H264R_OK;
-}
+int h264r_quant_init_lists(h264r_quant* q, const int32_t* const qm[12]) { return quant_init_lists(q, qm); }
 
 // Environment knobs, read and validated once (at the first h264r_create).  Each one only
 // chooses between bit-exact schedules or bounds a wait; a value out of its range fails
@@ -325,7 +138,7 @@ static int set_wait_bound(h264r_ctx* c, uint32_t ticks, hipStream_t s)
 {
     if (c->wait_ticks == ticks) return H264R_OK;
     c->wait_val = ticks;
-    HIP_OK(hipMemcpyAsync(c->d_err + 1, &c->wait_val, sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(c->d_err.p + 1, &c->wait_val, sizeof(uint32_t), hipMemcpyHostToDevice, s));
     c->wait_ticks = ticks;
     return H264R_OK;
 }
@@ -346,15 +159,15 @@ int h264r_create(h264r_ctx** out, int device, int max_w, int max_h, int chroma_f
     c->device = device; c->max_w = max_w; c->max_h = max_h; c->fmt = chroma_format_idc;
     // the context's own stream is a BLOCKING stream: work on the legacy NULL stream (torch's
     // default stream) and this stream are ordered with each other
+    // whatever fails, the context releases what it holds so far (h264r_destroy)
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_ref_planes), sizeof(uint8_t*) * 3 * H264R_MAX_SLOTS) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->d_err), 2 * sizeof(int)) != hipSuccess) {
-        delete c;
+        c->d_ref_planes.reserve(3 * H264R_MAX_SLOTS) != H264R_OK || c->d_err.reserve(2) != H264R_OK ||
+        hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming) != hipSuccess) {
+        (void)h264r_destroy(c);
         return H264R_EDEVICE;
     }
-    if (hipEventCreateWithFlags(&c->ev_last, hipEventDisableTiming) != hipSuccess) { delete c; return H264R_EDEVICE; }
-    (void)hipMemset(c->d_ref_planes, 0, sizeof(uint8_t*) * 3 * H264R_MAX_SLOTS);
-    (void)hipMemset(c->d_err, 0, 2 * sizeof(int));
+    (void)hipMemset(c->d_ref_planes.p, 0, sizeof(uint8_t*) * 3 * H264R_MAX_SLOTS);
+    (void)hipMemset(c->d_err.p, 0, 2 * sizeof(int));
     if (set_wait_bound(c, wait_bound_ticks(), c->stream) != H264R_OK || hipStreamSynchronize(c->stream) != hipSuccess) {
         (void)h264r_destroy(c);
         return H264R_EDEVICE;
@@ -368,36 +181,12 @@ int h264r_destroy(h264r_ctx* c)
     if (!c) return H264R_EINVAL;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (int s = 0; s < H264R_MAX_SLOTS; ++s) if (c->slot[s][0]) (void)hipFree(c->slot[s][0]);
-    void* bufs[] = {c->d_ref_planes, c->d_err, c->d_mbs, c->d_levels, c->d_mv, c->d_ref, c->d_slices, c->d_pic, c->d_quant, c->d_out,
-                    c->d_fpoc,
-                    c->d444_mbs, c->d444_slices, c->d444_quant, c->d444_refs, c->d444_chroma};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    for (auto& p : c->sp) {
-        if (p.out) (void)hipHostFree(p.out);
-        if (p.done) (void)hipEventDestroy(p.done);
-    }
-    c->sc.release();
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->ev_last) (void)hipEventDestroy(c->ev_last);
     if (c->side) (void)hipStreamSynchronize(c->side);
-    for (hipEvent_t e : c->ev_chunk) (void)hipEventDestroy(e);
-    if (c->ev_side) (void)hipEventDestroy(c->ev_side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return H264R_OK;
 }
 
-// Bytes of one chroma plane of a w x h MB picture: 8 x 8 samples per MB (4:2:0), 8 x 16 (4:2:2)
-// or 16 x 16 (4:4:4).
-static size_t chroma_bytes(const h264r_ctx* c, int w, int h)
-{
-    return (size_t)w * h * (c->fmt == 3 ? 256 : c->fmt == 2 ? 128 : c->fmt == 1 ? 64 : 0);     // 4:0:0: none
-}
-
-static int ensure_slot(h264r_ctx* c, int slot, int w, int h)
+int h264r::ensure_slot(h264r_ctx* c, int slot, int w, int h)
 {
     if (c->slot[slot][0] && c->slot_w[slot] == w && c->slot_h[slot] == h) return H264R_OK;
     if (c->slot[slot][0]) {
@@ -410,7 +199,7 @@ static int ensure_slot(h264r_ctx* c, int slot, int w, int h)
     if (hipMalloc(reinterpret_cast<void**>(&base), ys + 2 * cs + H264R_PLANE_SLACK) != hipSuccess) return H264R_ENOMEM;
     c->slot[slot][0] = base; c->slot[slot][1] = base + ys; c->slot[slot][2] = base + ys + cs;
     c->slot_w[slot] = w; c->slot_h[slot] = h;
-    HIP_OK(hipMemcpy(c->d_ref_planes + 3 * slot, c->slot[slot], 3 * sizeof(uint8_t*), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(c->d_ref_planes.p + 3 * slot, c->slot[slot], 3 * sizeof(uint8_t*), hipMemcpyHostToDevice));
     return H264R_OK;
 }
 
@@ -538,7 +327,7 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
         // zeroes the stage's sync words and the level counters
         if (++X.tag <= 0) X.tag = 1;
         hipLaunchKernelGGL(k_inter4r, igrid, dim3(256), 0, s, b, S.dbinfo, rows, S.sp_flag, recon, X.tag, sync,
-                           (int)SW.zeroed(), levels ? X.d_lcnt : nullptr, levels ? 3 * LEVEL_IDS : 0);
+                           (int)SW.zeroed(), levels ? X.d_lcnt.p : nullptr, levels ? 3 * LEVEL_IDS : 0);
         HIP_OK(hipGetLastError());
         // inter MBs of SP slices (a short launch when the batch has none)
         hipLaunchKernelGGL(k_inter_sp, dim3(1024), dim3(256), 0, s, b, rows, (const int*)S.sp_flag, recon, X.tag);
@@ -546,21 +335,21 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
     }
     {
         Timed t(c, 1, s);
-        uint16_t* lvl = levels ? X.d_lvl : nullptr;
+        uint16_t* lvl = levels ? X.d_lvl.p : nullptr;
         int* pband = sync + SW.pband();                         // after the zeroed words
         int* lbar = sync + SW.barrier();                        // k_intra_levels' barrier
         const int lmax = levels ? level_launches((size_t)P * W * HB) : 0;
         if (knobs().verbose) fprintf(stderr, "h264r: %d intra levels from lists, %d pictures\n", lmax, P);
         if (levels) {
             int* lvsync = sync + SW.level();
-            int* lcount = X.d_lcnt;
+            int* lcount = X.d_lcnt.p;
             int* lbase = lcount + LEVEL_IDS;
             int* lcursor = lbase + LEVEL_IDS;
             // pictures deeper than 4 x lmax levels (all-intra) are left to the walk whole
             hipLaunchKernelGGL(k_level, dim3(P), dim3(1024), 0, s, b, lvl, lvsync, lcount, rows, 4 * lmax, lmax, pband);
             HIP_OK(hipGetLastError());
             hipLaunchKernelGGL(k_level_scatter, dim3(P), dim3(1024), 0, s, b, (const uint16_t*)lvl, (const int*)lcount, lbase,
-                               lcursor, X.d_list, rows);
+                               lcursor, X.d_list.p, rows);
             HIP_OK(hipGetLastError());
             // the grid one block per CU below the occupancy answer, all resident at once (the grid
             // barrier's contract, include/h264r.h); a plain launch by default, H264R_COOP=1 a
@@ -573,9 +362,9 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
             if (coop) {
                 const int* lcount_c = lcount;
                 const int* lbase_c = lbase;
-                const uint32_t* list_c = X.d_list;
+                const uint32_t* list_c = X.d_list.p;
                 int lmax_v = lmax;
-                int* err_p = c->d_err;
+                int* err_p = c->d_err.p;
                 h264r_batch bv = b;
                 void* args[] = {(void*)&bv, (void*)&lcount_c, (void*)&lbase_c, (void*)&list_c, (void*)&lmax_v,
                                 (void*)&lvsync, (void*)&err_p, (void*)&recon, (void*)&lbar};
@@ -583,14 +372,14 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
                                                   dim3(256), args, 0, s));
             } else {
                 hipLaunchKernelGGL(k_intra_levels, dim3(lgrid), dim3(256), 0, s, b, (const int*)lcount,
-                                   (const int*)lbase, (const uint32_t*)X.d_list, lmax, lvsync, c->d_err, recon, lbar);
+                                   (const int*)lbase, (const uint32_t*)X.d_list.p, lmax, lvsync, c->d_err.p, recon, lbar);
                 HIP_OK(hipGetLastError());
             }
         }
         // the walk's band-to-band hand-off: global progress every gstep MBs (k_picture.hip);
         // H264R_WALK_GSTEP overrides
         const int gstep = wait_test ? -1 : K.walk_gstep > 0 ? K.walk_gstep : (P >= 128 ? 64 : 1);
-        hipLaunchKernelGGL(k_intra_pic, dim3(P * nbands), dim3(64 * H264R_WALK_ROWS), 0, s, b, sync, c->d_err,
+        hipLaunchKernelGGL(k_intra_pic, dim3(P * nbands), dim3(64 * H264R_WALK_ROWS), 0, s, b, sync, c->d_err.p,
                            (const uint16_t*)lvl, lmax, rows, gstep, recon, (const int*)pband);
         HIP_OK(hipGetLastError());
     }
@@ -640,24 +429,24 @@ static int deblock_launch(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
             HIP_OK(hipEventRecord(c->ev_fork, s));
             HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
             hipLaunchKernelGGL(k_deblock2c, dim3(grid), dim3(64), 0, c->side, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb),
-                               S.sync + SW.tickets_c(), c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
+                               S.sync + SW.tickets_c(), c->d_err.p, epoch, rows, nx, (const uint8_t*)S.recon);
             HIP_OK(hipGetLastError());
             hipLaunchKernelGGL(k_deblock2y, dim3(grid), dim3(64), 0, s, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb),
-                               dsync, c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
+                               dsync, c->d_err.p, epoch, rows, nx, (const uint8_t*)S.recon);
             HIP_OK(hipGetLastError());
             HIP_OK(hipEventRecord(c->ev_side, c->side));
             HIP_OK(hipStreamWaitEvent(s, c->ev_side, 0));
             return H264R_OK;
         }
         hipLaunchKernelGGL(k_deblock2, dim3(grid), dim3(64), 0, s, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb), dsync,
-                           c->d_err, epoch, rows, nx, (const uint8_t*)S.recon);
+                           c->d_err.p, epoch, rows, nx, (const uint8_t*)S.recon);
     } else {
         // k_deblock keeps a picture's pairs on one XCD (p % nx): nx times the largest
         // XCD share of waves, so every XCD runs all its pairs at once
         const int nx = c->nxcc > 1 && !(c->debug & H264R_DBG_DEBLOCK_GLOBAL) ? c->nxcc : 1;
         const int grid = nx * ((P + nx - 1) / nx) * npairs;
         hipLaunchKernelGGL(k_deblock, dim3(grid), dim3(64), 0, s, b, S.dbinfo, reinterpret_cast<uint64_t*>(hb), dsync,
-                           c->d_err, epoch, rows, nx, S.recon);
+                           c->d_err.p, epoch, rows, nx, S.recon);
     }
     HIP_OK(hipGetLastError());
     return H264R_OK;
@@ -697,10 +486,10 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
     if (nch < 2 || wait_test || (c->debug & H264R_DBG_NO_DEBLOCK)) nch = 1;
     const int chunk_min = P / nch;
     int st;
-    if ((st = dev_resize(&X.d_dbinfo, &X.c_dbinfo, (size_t)P * nmb * sizeof(DbInfo)))) return st;
+    if ((st = X.d_dbinfo.reserve((size_t)P * nmb * sizeof(DbInfo)))) return st;
     // the reconstruction kernels write the MB-tiled samples (device_common.h), the
     // deblocking kernel (or k_untile) turns them into the output planes
-    if ((st = dev_resize(&X.d_recon, &X.c_recon, (size_t)P * nmb * 384))) return st;
+    if ((st = X.d_recon.reserve((size_t)P * nmb * 384))) return st;
     // k_deblock2 needs many (picture group, band) walks in flight: H264R_DEBLOCK2_MIN is the
     // crossover measured on whole 1080p pictures (68 MB rows), so a launch qualifies by its
     // picture-rows (a 2160p picture counts twice, a 17-row slice band a quarter); the chunks of
@@ -717,28 +506,25 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
     const bool by_rows = sched != 0;                 // k_deblock2's hand-off records (both widths)
     // hand-off records of the chosen deblocking kernel, a region per picture; fresh memory or a
     // wrapping epoch restarts from zeroed records, so no record may carry a live tag
-    uint8_t** hb = by_rows ? &X.d_hb2 : &X.d_hb;
-    size_t* hcap = by_rows ? &X.c_hb2 : &X.c_hb;
+    DevBuf<uint8_t>& hb = by_rows ? X.d_hb2 : X.d_hb;
     uint32_t* ep = by_rows ? &X.epoch2 : &X.epoch;
     const uint32_t ep_max = by_rows ? (1u << 20) - 2 - 16 : 0xFFFFFF00u;
     const size_t hb_pic = by_rows ? (size_t)W * HANDOFF2_BYTES : (size_t)npairs * W * HANDOFF_BYTES;
     {
-        const size_t cap_before = *hcap;
-        if ((st = dev_resize(hb, hcap, (size_t)P * hb_pic))) return st;
-        if (*hcap != cap_before || *ep > ep_max) {
-            HIP_OK(hipMemsetAsync(*hb, 0, *hcap, s));
+        const size_t cap_before = hb.cap;
+        if ((st = hb.reserve((size_t)P * hb_pic))) return st;
+        if (hb.cap != cap_before || *ep > ep_max) {
+            HIP_OK(hipMemsetAsync(hb.p, 0, hb.cap, s));
             *ep = 0;
         }
     }
     // a sync region per chunk, sized for the largest chunk; each stage's k_inter4r zeroes its own
     // words, and k_level writes its pband words before k_intra_pic reads them
     const size_t sync_stride = SyncWords{chunk_min + 1, H}.total();
-    if ((st = dev_resize(&X.d_sync, &X.c_sync, (size_t)nch * sync_stride))) return st;
-    if (!X.d_sptag) {
-        int* t = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&t), OVERLAP_MAX * sizeof(int)) != hipSuccess) return H264R_ENOMEM;
-        if (hipMemsetAsync(t, 0, OVERLAP_MAX * sizeof(int), s) != hipSuccess) { (void)hipFree(t); return H264R_EDEVICE; }
-        X.d_sptag = t;
+    if ((st = X.d_sync.reserve((size_t)nch * sync_stride))) return st;
+    if (!X.d_sptag.p) {
+        if ((st = X.d_sptag.reserve(OVERLAP_MAX))) return st;
+        if (hipMemsetAsync(X.d_sptag.p, 0, OVERLAP_MAX * sizeof(int), s) != hipSuccess) { X.d_sptag.reset(); return H264R_EDEVICE; }
     }
     // H264R_DBG_WAIT_TEST: every intra-walk wait asks for progress no row reaches, under a
     // 10 ms bound -- the launch must drain and h264r_check report H264R_EDEVICE
@@ -756,9 +542,9 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
         if (K.verbose)
             fprintf(stderr, "h264r: k_intra_levels occupancy %d blocks/CU, %d CUs, grid %d\n", per_cu, cus, c->levels_grid);
     }
-    if (levels && ((st = dev_resize(&X.d_lvl, &X.c_lvl, (size_t)P * nmb)) ||
-                   (st = dev_resize(&X.d_list, &X.c_list, (size_t)P * nmb)) ||
-                   (st = dev_resize(&X.d_lcnt, &X.c_lcnt, 3 * (size_t)LEVEL_IDS))))
+    if (levels && ((st = X.d_lvl.reserve((size_t)P * nmb)) ||
+                   (st = X.d_list.reserve((size_t)P * nmb)) ||
+                   (st = X.d_lcnt.reserve(3 * (size_t)LEVEL_IDS))))
         return st;
     if (nch > 1) {
         if (!c->side) HIP_OK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
@@ -773,9 +559,9 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
     if (c->timing) c->timed_launches++;
     for (int k = 0, p0 = 0; k < nch; ++k) {
         const int n = P / nch + (k < P % nch ? 1 : 0);
-        Stage S{nch > 1 ? sub_batch(b, p0, n) : b, reinterpret_cast<DbInfo*>(X.d_dbinfo) + (size_t)p0 * nmb,
-                X.d_recon + (size_t)p0 * nmb * 384,
-                X.d_sync + (size_t)k * sync_stride, X.d_sptag + k};
+        Stage S{nch > 1 ? sub_batch(b, p0, n) : b, reinterpret_cast<DbInfo*>(X.d_dbinfo.p) + (size_t)p0 * nmb,
+                X.d_recon.p + (size_t)p0 * nmb * 384,
+                X.d_sync.p + (size_t)k * sync_stride, X.d_sptag.p + k};
         if ((st = recon_launches(c, S, s, rows, X, levels, K.coop && nch == 1))) return st;
         hipStream_t ds = s;
         if (nch > 1) {
@@ -783,13 +569,38 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
             HIP_OK(hipStreamWaitEvent(c->side, c->ev_chunk[k], 0));
             ds = c->side;
         }
-        if ((st = deblock_launch(c, S, ds, rows, *hb + (size_t)p0 * hb_pic, ++*ep, sched))) return st;
+        if ((st = deblock_launch(c, S, ds, rows, hb.p + (size_t)p0 * hb_pic, ++*ep, sched))) return st;
         p0 += n;
     }
     if (nch > 1) {
         HIP_OK(hipEventRecord(c->ev_side, c->side));
         HIP_OK(hipStreamWaitEvent(s, c->ev_side, 0));
     }
+    return H264R_OK;
+}
+
+// The batch derived for one pass over b (k_derive444: plane pl in the luma slots, with colour plane
+// qpl's lists): records, slices, quant and DPB tables in the context's one derived set, the pass's
+// own (empty) 4:2:0 chroma outputs in scratch.  *d is b rewired to them; out_y is the caller's.
+static int derive_batch(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int pl, int qpl, h264r_batch* d)
+{
+    const int P = b.num_pics;
+    const size_t nmb = (size_t)b.width_mbs * b.height_mbs;
+    const int ntab = b.ref_planes_stride ? P : 1;
+    int st;
+    if ((st = c->d444_mbs.reserve((size_t)P * nmb)) || (st = c->d444_slices.reserve((size_t)P * b.slice_stride)) ||
+        (st = c->d444_quant.reserve((size_t)P)) || (st = c->d444_refs.reserve((size_t)ntab * 3 * H264R_MAX_SLOTS)) ||
+        (st = c->d444_chroma.reserve((size_t)P * 2 * 64 * nmb + H264R_PLANE_SLACK)))
+        return st;
+    hipLaunchKernelGGL(k_derive444, dim3(1024), dim3(256), 0, s, b, pl, qpl, c->d444_mbs.p, c->d444_slices.p, c->d444_quant.p,
+                       c->d444_refs.p, ntab, c->d_err.p);
+    HIP_OK(hipGetLastError());
+    *d = b;
+    d->mbs = c->d444_mbs.p; d->slices = c->d444_slices.p; d->quant = c->d444_quant.p;
+    d->ref_planes = c->d444_refs.p;
+    d->ref_planes_stride = b.ref_planes_stride ? 3 * H264R_MAX_SLOTS : 0;
+    d->out_u = c->d444_chroma.p;
+    d->out_v = c->d444_chroma.p + (size_t)P * 64 * nmb;
     return H264R_OK;
 }
 
@@ -803,28 +614,12 @@ static int launch_all(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row
 // (empty) chroma goes to scratch.  The passes are stream-ordered and reuse one derived set.
 static int run_444(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, int row1)
 {
-    const int P = b.num_pics;
-    const size_t nmb = (size_t)b.width_mbs * b.height_mbs;
-    const int ntab = b.ref_planes_stride ? P : 1;
-    int st;
-    if ((st = dev_resize(&c->d444_mbs, &c->c444_mbs, (size_t)P * nmb)) ||
-        (st = dev_resize(&c->d444_slices, &c->c444_slices, (size_t)P * b.slice_stride)) ||
-        (st = dev_resize(&c->d444_quant, &c->c444_quant, (size_t)P)) ||
-        (st = dev_resize(&c->d444_refs, &c->c444_refs, (size_t)ntab * 3 * H264R_MAX_SLOTS)) ||
-        (st = dev_resize(&c->d444_chroma, &c->c444_chroma, (size_t)P * 2 * 64 * nmb + H264R_PLANE_SLACK)))
-        return st;
     const bool timing = c->timing;
+    int st;
     for (int pl = 0; pl < 3; ++pl) {
-        hipLaunchKernelGGL(k_derive444, dim3(1024), dim3(256), 0, s, b, pl, pl, c->d444_mbs, c->d444_slices, c->d444_quant,
-                           c->d444_refs, ntab, c->d_err);
-        HIP_OK(hipGetLastError());
-        h264r_batch d = b;
-        d.mbs = c->d444_mbs; d.slices = c->d444_slices; d.quant = c->d444_quant;
-        d.ref_planes = c->d444_refs;
-        d.ref_planes_stride = b.ref_planes_stride ? 3 * H264R_MAX_SLOTS : 0;
+        h264r_batch d;
+        if ((st = derive_batch(c, b, s, pl, pl, &d))) return st;
         d.out_y = pl == 0 ? b.out_y : pl == 1 ? b.out_u : b.out_v;
-        d.out_u = c->d444_chroma;
-        d.out_v = c->d444_chroma + (size_t)P * 64 * nmb;
         if ((st = launch_all(c, d, s, row0, row1, c->sc))) return st;
     }
     if (timing) c->timed_launches -= 2;            // h264r_last_timing: per batch, its three passes together
@@ -839,47 +634,32 @@ static int run_444(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, 
 static int run_422(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, int row1)
 {
     const int P = b.num_pics;
-    const size_t nmb = (size_t)b.width_mbs * b.height_mbs;
-    const int ntab = b.ref_planes_stride ? P : 1;
-    int st;
-    if ((st = dev_resize(&c->d444_mbs, &c->c444_mbs, (size_t)P * nmb)) ||
-        (st = dev_resize(&c->d444_slices, &c->c444_slices, (size_t)P * b.slice_stride)) ||
-        (st = dev_resize(&c->d444_quant, &c->c444_quant, (size_t)P)) ||
-        (st = dev_resize(&c->d444_refs, &c->c444_refs, (size_t)ntab * 3 * H264R_MAX_SLOTS)) ||
-        (st = dev_resize(&c->d444_chroma, &c->c444_chroma, (size_t)P * 2 * 64 * nmb + H264R_PLANE_SLACK)))
-        return st;
     // a separate-colour-plane (JV) batch on a 4:4:4 context: monochrome records, colour plane
     // jv - 1's lists, references and output plane (h264r_batch.colour_plane)
     const int jv = b.colour_plane;
-    hipLaunchKernelGGL(k_derive444, dim3(1024), dim3(256), 0, s, b, 0, jv ? jv - 1 : 0, c->d444_mbs, c->d444_slices,
-                       c->d444_quant, c->d444_refs, ntab, c->d_err);
-    HIP_OK(hipGetLastError());
-    h264r_batch d = b;
+    h264r_batch d;
+    int st;
+    if ((st = derive_batch(c, b, s, 0, jv ? jv - 1 : 0, &d))) return st;
     d.colour_plane = 0;
     if (jv) d.out_y = jv == 1 ? b.out_y : jv == 2 ? b.out_u : b.out_v;
-    d.mbs = c->d444_mbs; d.slices = c->d444_slices; d.quant = c->d444_quant;
-    d.ref_planes = c->d444_refs;
-    d.ref_planes_stride = b.ref_planes_stride ? 3 * H264R_MAX_SLOTS : 0;
-    d.out_u = c->d444_chroma;
-    d.out_v = c->d444_chroma + (size_t)P * 64 * nmb;
     if ((st = launch_all(c, d, s, row0, row1, c->sc))) return st;
     if (c->fmt == 0 || jv) return H264R_OK;                 // 4:0:0 / one JV plane: no chroma
     const int2 rows = make_int2(row0, row1);
     {
         Timed t(c, 0, s);
         const int64_t mbs = (int64_t)P * (row1 - row0) * b.width_mbs;
-        hipLaunchKernelGGL(k_c422_inter, dim3((unsigned)((mbs + 3) / 4)), dim3(256), 0, s, b, rows, c->d_err);
+        hipLaunchKernelGGL(k_c422_inter, dim3((unsigned)((mbs + 3) / 4)), dim3(256), 0, s, b, rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     {
         Timed t(c, 1, s);
-        hipLaunchKernelGGL(k_c422_intra, dim3(P), dim3(1024), 0, s, b, rows, c->d_err);
+        hipLaunchKernelGGL(k_c422_intra, dim3(P), dim3(1024), 0, s, b, rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     if (!((c->debug | knobs().debug) & H264R_DBG_NO_DEBLOCK)) {
         Timed t(c, 2, s);
         hipLaunchKernelGGL(k_c422_db, dim3(P), dim3(1024), 0, s, b,
-                           reinterpret_cast<const h264r::DbInfo*>(c->sc.d_dbinfo), rows, c->d_err);
+                           reinterpret_cast<const h264r::DbInfo*>(c->sc.d_dbinfo.p), rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     return H264R_OK;
@@ -903,33 +683,39 @@ static int run_mbaff(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0
     if (c->timing) c->timed_launches++;
     {
         Timed t(c, 0, s);
-        hipLaunchKernelGGL(k_mbaff_inter, dim3((unsigned)((size_t)P * W * (row1 - row0))), dim3(256), 0, s, b, rows, c->d_err);
+        hipLaunchKernelGGL(k_mbaff_inter, dim3((unsigned)((size_t)P * W * (row1 - row0))), dim3(256), 0, s, b, rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     {
         Timed t(c, 1, s);
         for (int d = d0; d < d1; ++d)
-            hipLaunchKernelGGL(k_mbaff_intra, dim3((unsigned)(P * HP)), dim3(256), 0, s, b, d, rows, c->d_err);
+            hipLaunchKernelGGL(k_mbaff_intra, dim3((unsigned)(P * HP)), dim3(256), 0, s, b, d, rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     if (!((c->debug | knobs().debug) & H264R_DBG_NO_DEBLOCK)) {
         Timed t(c, 2, s);
         for (int d = d0; d < d1; ++d)
-            hipLaunchKernelGGL(k_mbaff_deblock, dim3((unsigned)(P * HP)), dim3(64), 0, s, b, d, rows, c->d_err);
+            hipLaunchKernelGGL(k_mbaff_deblock, dim3((unsigned)(P * HP)), dim3(64), 0, s, b, d, rows, c->d_err.p);
         HIP_OK(hipGetLastError());
     }
     return H264R_OK;
 }
 
-static int run_batch(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, int row1)
+// The scratch and the planes are shared by every launch of this context: a launch on another
+// stream than the previous one waits for it first.
+int h264r::order_after_last(h264r_ctx* c, hipStream_t s)
 {
-    // the scratch is shared by every launch of this context: a launch on another stream
-    // than the previous one waits for it first
     if (c->last_stream && c->last_stream != s) {
         HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
         HIP_OK(hipStreamWaitEvent(s, c->ev_last, 0));
     }
     c->last_stream = s;
+    return H264R_OK;
+}
+
+int h264r::run_batch(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0, int row1)
+{
+    if (const int st = order_after_last(c, s)) return st;
     if (b.mbaff) return run_mbaff(c, b, s, row0, row1);
     if (b.colour_plane) {                                   // JV: one colour plane on a 4:4:4 context
         if (c->fmt != 3) return H264R_EUNSUPPORTED;
@@ -942,10 +728,12 @@ static int run_batch(h264r_ctx* c, const h264r_batch& b, hipStream_t s, int row0
 }
 
 #ifdef H264R_TRACE
+extern "C" {
 void h264r_db_trace_copy(void* dst);    // k_deblock.hip / k_deblock2.hip (trace builds)
 void h264r_db2_trace_copy(void* dst);
 void h264r_db2y_trace_copy(void* dst);
 void h264r_db2c_trace_copy(void* dst);
+}
 // H264R_TRACE_OUT=<path>: k_deblock's trace to <path>, k_deblock2's to <path>.2, the split walk's to .2y / .2c
 static void dump_trace(hipStream_t s)
 {
@@ -989,7 +777,7 @@ int h264r_decode_batch(h264r_ctx* c, const h264r_batch* b, void* stream)
     if (!batch_ok(c, b)) return H264R_EINVAL;
     (void)hipSetDevice(c->device);
     h264r_batch bb = *b;
-    if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes;
+    if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes.p;
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
 #ifdef H264R_TRACE
     int st = run_batch(c, bb, s, 0, bb.height_mbs);
@@ -1005,7 +793,7 @@ int h264r_decode_batch_rows(h264r_ctx* c, const h264r_batch* b, int row0, int ro
     if (!batch_ok(c, b) || row0 < 0 || row1 <= row0 || row1 > b->height_mbs) return H264R_EINVAL;
     (void)hipSetDevice(c->device);
     h264r_batch bb = *b;
-    if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes;
+    if (!bb.ref_planes) bb.ref_planes = c->d_ref_planes.p;
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
     return run_batch(c, bb, s, row0, row1);
 }
@@ -1028,8 +816,8 @@ int h264r_check(h264r_ctx* c)
     if (c->last_stream) HIP_OK(hipStreamSynchronize(c->last_stream));
     if (c->side) HIP_OK(hipStreamSynchronize(c->side));
     int e = 0;
-    HIP_OK(hipMemcpy(&e, c->d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (e) { (void)hipMemset(c->d_err, 0, sizeof(int)); return H264R_EDEVICE; }
+    HIP_OK(hipMemcpy(&e, c->d_err.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (e) { (void)hipMemset(c->d_err.p, 0, sizeof(int)); return H264R_EDEVICE; }
     return H264R_OK;
 }
 
@@ -1058,531 +846,6 @@ int h264r_last_timing(h264r_ctx* c, float out[4])
     c->timed_launches = 0;
     return H264R_OK;
 }
-
-// ------------------------------------------------------------- output stage (h264r_output.h)
-// The planes of one output frame: the geometry (output.cc:135-165) and the layout, as the job k_output
-// takes and, for the caller, as an h264r_out_geom.
-static int output_plan(int fmt, const h264r_out_desc* d, h264r_out_geom* g, h264r::OutJob* job)
-{
-    if (!d || fmt < 0 || fmt > 3 || d->width_mbs <= 0 || d->frame_height_mbs <= 0 ||
-        d->width_mbs > H264R_OUT_MAX_MBS || d->frame_height_mbs > H264R_OUT_MAX_MBS ||
-        (d->frame_mbs_only != 0 && d->frame_mbs_only != 1) ||
-        (d->layout != H264R_OUT_PLANAR && d->layout != H264R_OUT_SEMIPLANAR))
-        return H264R_EINVAL;
-    const int pa = d->pitch_align;
-    if (pa < 0 || pa > H264R_OUT_MAX_PITCH_ALIGN || (pa & (pa - 1))) return H264R_EINVAL;
-    if (d->crop_left < 0 || d->crop_right < 0 || d->crop_top < 0 || d->crop_bottom < 0) return H264R_EINVAL;
-    if (d->fake_chroma && fmt != 0) return H264R_EUNSUPPORTED;
-    const int sub_w = (fmt == 1 || fmt == 2) ? 2 : 1, sub_h = fmt == 1 ? 2 : 1;    // 4:0:0: CropUnitX 1
-    const int mb_cw = fmt ? 16 / sub_w : 0, mb_ch = fmt ? 16 / sub_h : 0;
-    const int64_t uy = 2 - d->frame_mbs_only;
-    const int64_t lc = d->crop_left, rc = d->crop_right, tc = d->crop_top * uy, bc = d->crop_bottom * uy;
-    const int64_t lw = 16 * (int64_t)d->width_mbs - sub_w * (lc + rc);
-    const int64_t lh = 16 * (int64_t)d->frame_height_mbs - sub_h * (tc + bc);
-    const int64_t cw = fmt ? mb_cw * (int64_t)d->width_mbs - (lc + rc) : 0;
-    const int64_t ch = fmt ? mb_ch * (int64_t)d->frame_height_mbs - (tc + bc) : 0;
-    if (lw <= 0 || lh <= 0 || (fmt && (cw <= 0 || ch <= 0))) return H264R_EINVAL;
-
-    h264r::OutJob J{};
-    auto plane = [&](int mode, int64_t w, int64_t h, int64_t x0, int64_t y0, int src_pitch) {
-        h264r::OutPlane& p = J.pl[J.nplanes];
-        p.off = J.nplanes ? J.pl[J.nplanes - 1].off + J.pl[J.nplanes - 1].pitch * J.pl[J.nplanes - 1].h : 0;
-        p.pitch = pa > 1 ? (w + pa - 1) / pa * pa : w;
-        p.w = (int32_t)w; p.h = (int32_t)h; p.x0 = (int32_t)x0; p.y0 = (int32_t)y0;
-        p.src_pitch = src_pitch; p.mode = mode;
-        ++J.nplanes;
-    };
-    plane(h264r::OUT_COPY_Y, lw, lh, sub_w * lc, sub_h * tc, 16 * d->width_mbs);
-    const bool semi = d->layout == H264R_OUT_SEMIPLANAR;
-    if (fmt) {
-        const int cp = mb_cw * d->width_mbs;
-        if (semi) plane(h264r::OUT_INTERLEAVE, 2 * cw, ch, lc, tc, cp);
-        else { plane(h264r::OUT_COPY_U, cw, ch, lc, tc, cp); plane(h264r::OUT_COPY_V, cw, ch, lc, tc, cp); }
-    } else if (d->fake_chroma) {
-        const int64_t fu = lw * lh / 4;                          // WriteUV (output.cc:205-224): one run per plane
-        if (fu > 0) {
-            if (semi) plane(h264r::OUT_FILL, 2 * fu, 1, 0, 0, 0);
-            else { plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); }
-        }
-    }
-    J.need_chroma = fmt != 0;
-    const h264r::OutPlane& last = J.pl[J.nplanes - 1];
-    const int64_t frame_bytes = last.off + last.pitch * last.h;
-    if (g) {
-        *g = h264r_out_geom{};
-        const int32_t l[4] = {(int32_t)(sub_w * lc), (int32_t)(sub_h * tc), (int32_t)lw, (int32_t)lh};
-        const int32_t cr[4] = {(int32_t)lc, (int32_t)tc, (int32_t)cw, (int32_t)ch};
-        for (int k = 0; k < 4; ++k) { g->luma[k] = l[k]; g->chroma[k] = fmt ? cr[k] : 0; }
-        for (int k = 0; k < J.nplanes; ++k) { g->plane_off[k] = J.pl[k].off; g->plane_pitch[k] = J.pl[k].pitch; }
-        g->frame_bytes = frame_bytes;
-    }
-    if (job) { *job = J; job->frame_stride = frame_bytes; }
-    return H264R_OK;
-}
-
-// The stream an output launch goes to: the caller's, or the context's.  The sources are, as a rule, what
-// the context's last launch wrote: ordered as run_batch orders launches.
-static int output_stream(h264r_ctx* c, void* stream, hipStream_t* s)
-{
-    (void)hipSetDevice(c->device);
-    *s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
-    if (c->last_stream && c->last_stream != *s) {
-        HIP_OK(hipEventRecord(c->ev_last, c->last_stream));
-        HIP_OK(hipStreamWaitEvent(*s, c->ev_last, 0));
-    }
-    c->last_stream = *s;
-    return H264R_OK;
-}
-
-int h264r_output_geometry(int chroma_format_idc, const h264r_out_desc* desc, h264r_out_geom* geom)
-{
-    if (!geom) return H264R_EINVAL;
-    return output_plan(chroma_format_idc, desc, geom, nullptr);
-}
-
-int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_out_frame* frames, int num_frames,
-                        uint8_t* dst, int64_t dst_frame_stride, void* stream)
-{
-    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
-    h264r::OutJob job;
-    const int st = output_plan(c->fmt, desc, nullptr, &job);
-    if (st != H264R_OK) return st;
-    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
-    if (num_frames == 0) return H264R_OK;
-    job.frame_stride = dst_frame_stride;
-    job.num_frames = num_frames;
-    hipStream_t s;
-    if (const int e = output_stream(c, stream, &s)) return e;
-    int items = 0;
-    for (int k = 0; k < job.nplanes; ++k)
-        items = std::max(items, job.pl[k].h * h264r::out_chunks_per_row(job.pl[k].w));
-    const int per = h264r::OUT_THREADS * h264r::OUT_ITEMS;
-    const dim3 grid((unsigned)((items + per - 1) / per), (unsigned)std::min(num_frames, 65535), (unsigned)job.nplanes);
-    hipLaunchKernelGGL(k_output, grid, dim3(h264r::OUT_THREADS), 0, s, job, frames, dst, c->d_err);
-    HIP_OK(hipGetLastError());
-    return H264R_OK;
-}
-
-// ------------------------------------------------------------- RGB frames (h264r_output.h)
-int h264r_rgb_coefficients(int matrix, int full_range, int32_t out[6])
-{
-    // floor(real * 2^14 + 1/2) of the header's reals: cy, crv, cgu, cgv, cbu, yo
-    static const int32_t rows[3][2][6] = {
-        {{19077, 26149, -6419, -13320, 33050, 16}, {16384, 22970, -5638, -11700, 29032, 0}},   // BT.601
-        {{19077, 29372, -3494, -8731, 34610, 16}, {16384, 25802, -3069, -7670, 30402, 0}},     // BT.709
-        {{19077, 27503, -3069, -10657, 35091, 16}, {16384, 24160, -2696, -9361, 30825, 0}},    // BT.2020
-    };
-    if (!out || matrix < H264R_CSC_BT601 || matrix > H264R_CSC_BT2020 || (full_range != 0 && full_range != 1))
-        return H264R_EINVAL;
-    for (int k = 0; k < 6; ++k) out[k] = rows[matrix][full_range][k];
-    return H264R_OK;
-}
-
-// The layout of one RGB frame of w x h pixels: for the caller as an h264r_rgb_geom, and as the output
-// side of the job the RGB kernels take.
-static void rgb_layout(int format, int64_t pa, int64_t w, int64_t h, h264r_rgb_geom* g, h264r::RgbJob* job)
-{
-    const bool planar = format == H264R_RGB_PLANAR_U8 || format == H264R_RGB_PLANAR_F16;
-    const int64_t bpp = format == H264R_RGB_PACKED_U8 ? 3 : format == H264R_RGB_PACKED_U8X4 ? 4 :
-                        format == H264R_RGB_PLANAR_F16 ? 2 : 1;
-    const int64_t pitch = pa > 1 ? (bpp * w + pa - 1) / pa * pa : bpp * w;
-    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * h;
-    if (g) {
-        *g = h264r_rgb_geom{};
-        g->width = (int32_t)w; g->height = (int32_t)h;
-        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * h; g->plane_pitch[k] = pitch; }
-        g->frame_bytes = frame_bytes;
-    }
-    if (job) {
-        for (int k = 0; k < 3; ++k) job->plane_off[k] = planar ? k * pitch * h : 0;
-        job->pitch = pitch;
-        job->frame_stride = frame_bytes;
-    }
-}
-
-// what both RGB entry points require of dst: room for every frame, and binary16 at even addresses
-static bool rgb_dst_ok(const h264r::RgbJob& job, const void* dst, int64_t dst_frame_stride)
-{
-    if (dst_frame_stride < job.frame_stride) return false;
-    return job.format != H264R_RGB_PLANAR_F16 || !((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1);
-}
-
-// What RGB frames are made from: the descriptor checked, the size of the cropped rectangle of desc->src
-// (known wherever the status is H264R_OK or H264R_EUNSUPPORTED) and the source side of the job: all of
-// it but the layout.
-static int rgb_source(int fmt, const h264r_rgb_desc* d, int32_t size[2], h264r::RgbJob* job)
-{
-    if (!d || d->src.layout != H264R_OUT_PLANAR || d->src.fake_chroma != 0) return H264R_EINVAL;
-    h264r_out_geom og;
-    const int st = output_plan(fmt, &d->src, &og, nullptr);
-    if (st != H264R_OK) return st;
-    size[0] = og.luma[2]; size[1] = og.luma[3];
-    if (d->matrix < H264R_CSC_BT601 || d->matrix > H264R_CSC_GBR ||
-        (d->chroma_up != H264R_UP_REPLICATE && d->chroma_up != H264R_UP_BILINEAR) ||
-        d->format < H264R_RGB_PACKED_U8 || d->format > H264R_RGB_PLANAR_F16 ||
-        (d->full_range != 0 && d->full_range != 1) || (d->bgr != 0 && d->bgr != 1) || d->alpha < 0 || d->alpha > 255)
-        return H264R_EINVAL;
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(d->scale[k]) || !std::isfinite(d->bias[k])) return H264R_EINVAL;
-    if (d->matrix == H264R_CSC_GBR && fmt != 3) return H264R_EUNSUPPORTED;
-
-    if (job) {
-        h264r::RgbJob J{};
-        J.lw = og.luma[2]; J.lh = og.luma[3]; J.x0 = og.luma[0]; J.y0 = og.luma[1];
-        J.cx0 = og.chroma[0]; J.cy0 = og.chroma[1]; J.cw = og.chroma[2]; J.ch = og.chroma[3];
-        J.lpitch = 16 * d->src.width_mbs;
-        J.cpitch = fmt == 3 ? J.lpitch : fmt ? J.lpitch / 2 : 0;
-        J.sub_h = fmt == 1 ? 2 : 1;
-        const bool bil = d->chroma_up == H264R_UP_BILINEAR;
-        J.mode = fmt == 0 ? h264r::RGB_MONO : fmt == 3 ? (d->matrix == H264R_CSC_GBR ? h264r::RGB_GBR : h264r::RGB_FULL) :
-                 !bil ? h264r::RGB_REP : fmt == 2 ? h264r::RGB_BIL1 : h264r::RGB_BIL2;
-        J.format = d->format; J.bgr = d->bgr; J.alpha = d->alpha;
-        if (d->matrix != H264R_CSC_GBR) {
-            int32_t k[6];
-            h264r_rgb_coefficients(d->matrix, d->full_range, k);
-            J.cy = k[0]; J.crv = k[1]; J.cgu = k[2]; J.cgv = k[3]; J.cbu = k[4]; J.yo = k[5];
-        }
-        for (int k = 0; k < 3; ++k) { J.scale[k] = d->scale[k]; J.bias[k] = d->bias[k]; }
-        *job = J;
-    }
-    return H264R_OK;
-}
-
-// The layout of one RGB frame and the job k_output_rgb takes, from the geometry of desc->src.
-static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job)
-{
-    int32_t size[2];
-    const int st = rgb_source(fmt, d, size, job);
-    if (st == H264R_OK) rgb_layout(d->format, d->src.pitch_align, size[0], size[1], g, job);
-    return st;
-}
-
-int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc, h264r_rgb_geom* geom)
-{
-    if (!geom) return H264R_EINVAL;
-    return rgb_plan(chroma_format_idc, desc, geom, nullptr);
-}
-
-int h264r_output_rgb(h264r_ctx* c, const h264r_rgb_desc* desc, const h264r_out_frame* frames, int num_frames,
-                     void* dst, int64_t dst_frame_stride, void* stream)
-{
-    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
-    h264r::RgbJob job;
-    const int st = rgb_plan(c->fmt, desc, nullptr, &job);
-    if (st != H264R_OK) return st;
-    if (!rgb_dst_ok(job, dst, dst_frame_stride)) return H264R_EINVAL;
-    if (num_frames == 0) return H264R_OK;
-    job.frame_stride = dst_frame_stride;
-    job.num_frames = num_frames;
-    hipStream_t s;
-    if (const int e = output_stream(c, stream, &s)) return e;
-    const int units = job.lh * h264r::rgb_units_per_row(job.lw);
-    const int per = h264r::RGB_THREADS * h264r::RGB_ITEMS;
-    const dim3 grid((unsigned)((units + per - 1) / per), (unsigned)std::min(num_frames, 65535));
-    hipLaunchKernelGGL(k_output_rgb, grid, dim3(h264r::RGB_THREADS), 0, s, job, frames, static_cast<uint8_t*>(dst),
-                       c->d_err);
-    HIP_OK(hipGetLastError());
-    return H264R_OK;
-}
-
-// ------------------------------------------------------------- scaled RGB frames (h264r_output.h)
-static int64_t gcd64(int64_t a, int64_t b)
-{
-    while (b) { const int64_t t = a % b; a = b; b = t; }
-    return a;
-}
-
-// The layout of one scaled frame and the job the k_output_rgb_scaled kernels take.  Argument errors come before
-// what is merely unsupported, as in rgb_source.
-static int scale_plan(int fmt, const h264r_scale_desc* d, h264r_rgb_geom* g, h264r::ScaleJob* job)
-{
-    if (!d) return H264R_EINVAL;
-    int32_t full[2];                                         // rgb_source knows the size before it finds GBR off 4:4:4
-    h264r::RgbJob R;
-    const int st = rgb_source(fmt, &d->rgb, full, &R);
-    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
-    if (d->roi_x < 0 || d->roi_y < 0 || d->roi_w < 0 || d->roi_h < 0 || (d->roi_w == 0) != (d->roi_h == 0) ||
-        d->out_w < 1 || d->out_w > H264R_SCALE_MAX_OUT || d->out_h < 1 || d->out_h > H264R_SCALE_MAX_OUT ||
-        (d->filter != H264R_SCALE_BILINEAR && d->filter != H264R_SCALE_AREA) || d->pad != 0)
-        return H264R_EINVAL;
-    const int64_t sw = d->roi_w ? d->roi_w : full[0], sh = d->roi_h ? d->roi_h : full[1];
-    if (d->roi_x + sw > full[0] || d->roi_y + sh > full[1]) return H264R_EINVAL;
-    if (st != H264R_OK) return st;
-    const int64_t gw = gcd64(sw, d->out_w), gh = gcd64(sh, d->out_h);
-    const int64_t rw = sw / gw, rh = sh / gh;
-    if (d->filter == H264R_SCALE_AREA && rw * rh > h264r::SCALE_AREA_MAX_T) return H264R_EUNSUPPORTED;
-
-    rgb_layout(d->rgb.format, d->rgb.src.pitch_align, d->out_w, d->out_h, g, &R);
-    if (job) {
-        h264r::ScaleJob J{};
-        J.rgb = R;
-        auto axis = [](int64_t S, int64_t D, int64_t gc) {
-            h264r::ScaleAxis a;
-            a.S = (int32_t)S; a.D = (int32_t)D; a.s = (int32_t)(S / gc); a.d = (int32_t)(D / gc);
-            a.inv_d = 1.0f / (float)a.d; a.inv_2D = 1.0f / (float)(2 * a.D);
-            return a;
-        };
-        J.ax = axis(sw, d->out_w, gw);
-        J.ay = axis(sh, d->out_h, gh);
-        J.roi_x = d->roi_x; J.roi_y = d->roi_y;
-        J.filter = d->filter;
-        // the widest window of columns: floor(d s / D) .. ceil((d + 1) s / D) holds ceil(s / D) + 1 at most
-        // (bilinear: 2), and one more in front where the unit starts on the even column before it
-        const int64_t span = (d->filter == H264R_SCALE_AREA ? (J.ax.s + J.ax.d - 1) / J.ax.d + 1 : 2) + (R.mode >= h264r::RGB_REP ? 1 : 0);
-        J.taps = (int32_t)std::min<int64_t>(span, h264r::RGB_UNIT);
-        J.T = (uint32_t)(rw * rh);
-        J.inv_2T = 1.0f / (2.0f * (float)J.T);
-        *job = J;
-    }
-    return H264R_OK;
-}
-
-int h264r_output_rgb_scaled_geometry(int chroma_format_idc, const h264r_scale_desc* desc, h264r_rgb_geom* geom)
-{
-    if (!geom) return H264R_EINVAL;
-    return scale_plan(chroma_format_idc, desc, geom, nullptr);
-}
-
-int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h264r_out_frame* frames, int num_frames,
-                            void* dst, int64_t dst_frame_stride, void* stream)
-{
-    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
-    h264r::ScaleJob job;
-    const int st = scale_plan(c->fmt, desc, nullptr, &job);
-    if (st != H264R_OK) return st;
-    if (!rgb_dst_ok(job.rgb, dst, dst_frame_stride)) return H264R_EINVAL;
-    if (num_frames == 0) return H264R_OK;
-    job.rgb.frame_stride = dst_frame_stride;
-    job.rgb.num_frames = num_frames;
-    hipStream_t s;
-    if (const int e = output_stream(c, stream, &s)) return e;
-    // the kernel of the job's mode and filter; frame z * grid.y + y, so that one launch holds any number
-    using ScaleKernel = void (*)(h264r::ScaleJob, const h264r_out_frame*, uint8_t*, int*);
-    ScaleKernel kernel[h264r::RGB_BIL2 + 1][2] = {};
-#define H264R_SCALE_KERNEL_ENTRY(NAME, MODE, FILTER) kernel[MODE][FILTER] = k_output_rgb_scaled_##NAME;
-    H264R_SCALE_KERNELS(H264R_SCALE_KERNEL_ENTRY)
-#undef H264R_SCALE_KERNEL_ENTRY
-    const int units = job.ay.D * h264r::rgb_units_per_row(job.ax.D);
-    const int gy = std::min(num_frames, 65535);
-    const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
-    hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
-                       static_cast<uint8_t*>(dst), c->d_err);
-    HIP_OK(hipGetLastError());
-    return H264R_OK;
-}
-
-// ------------------------------------------------------------- streaming API
-int h264r_picture_begin(h264r_ctx* c, int w, int h, const h264r_pic* pic, const h264r_slice* slices,
-                        const h264r_quant* quant)
-{
-    if (!c || !pic || !slices || !quant || w <= 0 || h <= 0 || w > c->max_w || h > c->max_h ||
-        pic->num_slices <= 0 || pic->num_slices > H264R_MAX_SLICES)
-        return H264R_EINVAL;
-    // both staging pictures in flight: the caller collects one first (h264r_picture_wait)
-    if (c->sp_pending == 2) return H264R_ESTATE;
-    auto& P = c->sp[c->sp_fill];
-    P.pw = w; P.ph = h;
-    const size_t n = (size_t)w * h;
-    P.h_mbs.assign(n, h264r_mb{});
-    P.h_levels.clear();
-    P.h_mv.assign(2 * 16 * n, 0);
-    P.h_ref.assign(2 * 16 * n, -1);
-    P.h_slices.assign(slices, slices + pic->num_slices);
-    P.h_pic = *pic;
-    P.h_quant = *quant;
-    P.seen.assign(n, 0);
-    P.has_fpoc = false;                                        // a record covers one picture
-    c->in_pic = true;
-    return H264R_OK;
-}
-
-int h264r_picture_field_pocs(h264r_ctx* c, const h264r_field_poc* rec)
-{
-    if (!c) return H264R_EINVAL;
-    if (!c->in_pic) return H264R_ESTATE;
-    auto& P = c->sp[c->sp_fill];
-    if (!rec || P.h_pic.structure != H264R_MBAFF_FRAME) return H264R_EINVAL;
-    P.h_fpoc = *rec;
-    P.has_fpoc = true;
-    return H264R_OK;
-}
-
-int h264r_mb_submit(h264r_ctx* c, int addr, const h264r_mb* mb, const int16_t* levels, int n_levels,
-                    const uint32_t* mv, const int8_t* ref_idx)
-{
-    if (!c) return H264R_EINVAL;
-    if (!c->in_pic) return H264R_ESTATE;
-    auto& P = c->sp[c->sp_fill];
-    const int n = P.pw * P.ph;
-    if (addr < 0 || addr >= n || !mb || n_levels < 0 || (n_levels && !levels) || !mv || !ref_idx) return H264R_EINVAL;
-    if (mb->slice >= P.h_pic.num_slices) return H264R_EINVAL;
-    if (mb->mb_type == H264R_SI) return H264R_EUNSUPPORTED;        // see include/h264r.h
-    // lossless inter MBs: the kernels take intra_chroma_pred_mode as DC, which is what the
-    // parser leaves in an inter MB (macroblock_t::init, slice_data.cc:482)
-    if ((mb->flags & H264R_MBF_BYPASS) && !(mb->flags & H264R_MBF_INTRA) && mb->chroma_mode != 0) return H264R_EINVAL;
-    h264r_mb m = *mb;
-    // append the level block, 16-byte aligned
-    while (P.h_levels.size() % 8) P.h_levels.push_back(0);
-    m.coef_off = (uint32_t)P.h_levels.size();
-    P.h_levels.insert(P.h_levels.end(), levels, levels + n_levels);
-    P.h_mbs[addr] = m;
-    const int W4 = P.pw * 4, plane = W4 * P.ph * 4, x = addr % P.pw, y = addr / P.pw;
-    for (int l = 0; l < 2; ++l)
-        for (int k = 0; k < 16; ++k) {
-            int idx = (y * 4 + k / 4) * W4 + x * 4 + k % 4;
-            P.h_mv[(size_t)l * plane + idx] = mv[l * 16 + k];
-            P.h_ref[(size_t)l * plane + idx] = ref_idx[l * 16 + k];
-        }
-    P.seen[addr] = 1;
-    return H264R_OK;
-}
-
-int h264r_picture_end_async(h264r_ctx* c, int keep_slot)
-{
-    if (!c) return H264R_EINVAL;
-    if (!c->in_pic) return H264R_ESTATE;
-    c->in_pic = false;
-    auto& P = c->sp[c->sp_fill];
-    for (uint8_t s : P.seen) if (!s) return H264R_ESTATE;      // every MB must be submitted
-    if (keep_slot >= H264R_MAX_SLOTS) return H264R_EINVAL;
-    (void)hipSetDevice(c->device);
-    const size_t n = (size_t)P.pw * P.ph, ys = n * 256, cs = chroma_bytes(c, P.pw, P.ph);
-    if (P.h_levels.empty()) P.h_levels.push_back(0);
-    // 4:4:4: frame pictures only; a PCM MB's Cr view reads 128 entries past its block (run_444)
-    if (c->fmt != 1 && P.h_pic.structure != H264R_FRAME) return H264R_EUNSUPPORTED;
-    if (c->fmt != 1)                                       // SP slices are 4:2:0 only (Extended profile)
-        for (const h264r_slice& sl : P.h_slices) if (sl.slice_type == H264R_SLICE_SP) return H264R_EUNSUPPORTED;
-    if (c->fmt == 3) P.h_levels.insert(P.h_levels.end(), 128, 0);
-    if (c->fmt == 0) P.h_levels.insert(P.h_levels.end(), 64, 0);     // the luma pass's chroma view of a PCM MB
-    // every referenced slot must be loaded, with a frame of this picture's size (a field
-    // picture: twice its height; its entries may name either field of a slot, include/h264r.h)
-    const int fld = P.h_pic.structure == H264R_TOP_FIELD || P.h_pic.structure == H264R_BOTTOM_FIELD;
-    const int mbaff = P.h_pic.structure == H264R_MBAFF_FRAME;
-    if (P.h_pic.structure < H264R_FRAME || P.h_pic.structure > H264R_MBAFF_FRAME) return H264R_EINVAL;
-    if (mbaff) {
-        // MBAFF (include/h264r.h): 4:2:0, MB pairs, implicit weights only with the picture's field POCs
-        // (k_mbaff_inter flags the same cases, and an SP slice's 8x8 transforms and QsC >= 6, on the
-        // device: h264r_picture_wait)
-        if (P.ph & 1) return H264R_EINVAL;
-        for (const h264r_slice& sl : P.h_slices)
-            if (sl.wp_mode == 2 && !P.has_fpoc) return H264R_EUNSUPPORTED;
-        for (size_t a = 0; a < P.h_mbs.size(); a += 1) {
-            const size_t top = ((a / P.pw) & ~(size_t)1) * P.pw + a % P.pw;
-            if ((P.h_mbs[a].flags ^ P.h_mbs[top].flags) & H264R_MBF_FIELD) return H264R_EINVAL;   // one flag per pair
-        }
-        // a field MB's refIdx names field refIdx / 2 of the list
-        for (size_t a = 0; a < P.h_mbs.size(); ++a) {
-            const h264r_mb& m = P.h_mbs[a];
-            if (m.flags & H264R_MBF_INTRA) continue;
-            const int x = (int)(a % P.pw), y = (int)(a / P.pw), W4 = P.pw * 4, plane = W4 * P.ph * 4;
-            const int nr = (m.flags & H264R_MBF_FIELD) ? 2 : 1;
-            for (int l = 0; l < 2; ++l)
-                for (int k = 0; k < 16; ++k) {
-                    const int r = P.h_ref[(size_t)l * plane + (y * 4 + k / 4) * W4 + x * 4 + k % 4];
-                    if (r >= nr * P.h_slices[m.slice].num_ref[l]) return H264R_EINVAL;
-                }
-        }
-    } else if (c->fmt == 1)
-        for (const h264r_mb& m : P.h_mbs) if (m.flags & H264R_MBF_FIELD) return H264R_EINVAL;
-    const int frame_h = P.ph << fld;
-    for (const h264r_slice& sl : P.h_slices)
-        for (int l = 0; l < 2; ++l)
-            for (int i = 0; i < sl.num_ref[l]; ++i) {
-                const int ref = sl.ref_slot[l][i];
-                const int slot = fld ? ref & ~H264R_REF_BOTTOM : ref;
-                if (ref < 0 || slot >= H264R_MAX_SLOTS) return H264R_EINVAL;
-                if (!c->slot[slot][0] || c->slot_w[slot] != P.pw || c->slot_h[slot] != frame_h) return H264R_ESTATE;
-            }
-    int st = 0;
-    // the device inputs are one set, reused in stream order (dev_resize drains before it frees)
-    if ((st = dev_resize(&c->d_mbs, &c->c_mbs, n)) || (st = dev_resize(&c->d_levels, &c->c_levels, P.h_levels.size())) ||
-        (st = dev_resize(&c->d_mv, &c->c_mv, P.h_mv.size())) || (st = dev_resize(&c->d_ref, &c->c_ref, P.h_ref.size())) ||
-        (st = dev_resize(&c->d_slices, &c->c_slices, P.h_slices.size())) || (st = dev_resize(&c->d_pic, &c->c_pic, 1)) ||
-        (st = dev_resize(&c->d_quant, &c->c_quant, 1)) || (st = dev_resize(&c->d_out, &c->c_out, ys + 2 * cs)) ||
-        (P.has_fpoc && (st = dev_resize(&c->d_fpoc, &c->c_fpoc, 1))))
-        return st;
-    if (P.c_out < ys + 2 * cs + 16) {
-        if (P.out) (void)hipHostFree(P.out);
-        P.out = nullptr; P.c_out = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&P.out), ys + 2 * cs + 16) != hipSuccess) return H264R_ENOMEM;
-        P.c_out = ys + 2 * cs + 16;
-    }
-    if (!P.done) HIP_OK(hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
-    hipStream_t s = c->stream;
-    HIP_OK(hipMemcpyAsync(c->d_mbs, P.h_mbs.data(), n * sizeof(h264r_mb), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_levels, P.h_levels.data(), P.h_levels.size() * 2, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_mv, P.h_mv.data(), P.h_mv.size() * 4, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_ref, P.h_ref.data(), P.h_ref.size(), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_slices, P.h_slices.data(), P.h_slices.size() * sizeof(h264r_slice), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_pic, &P.h_pic, sizeof(h264r_pic), hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(c->d_quant, &P.h_quant, sizeof(h264r_quant), hipMemcpyHostToDevice, s));
-    if (P.has_fpoc) HIP_OK(hipMemcpyAsync(c->d_fpoc, &P.h_fpoc, sizeof(h264r_field_poc), hipMemcpyHostToDevice, s));
-    h264r_batch b{};
-    b.num_pics = 1; b.width_mbs = P.pw; b.height_mbs = P.ph; b.slice_stride = (int)P.h_slices.size();
-    b.mbs = c->d_mbs; b.levels = c->d_levels; b.mv = c->d_mv; b.ref_idx = c->d_ref; b.slices = c->d_slices;
-    b.pics = c->d_pic; b.quant = c->d_quant; b.ref_planes = c->d_ref_planes;
-    b.out_y = c->d_out; b.out_u = c->d_out + ys; b.out_v = c->d_out + ys + cs;
-    b.mbaff = mbaff;
-    b.field_poc = P.has_fpoc ? c->d_fpoc : nullptr;
-    if ((st = run_batch(c, b, s, 0, b.height_mbs))) return st;
-    if (keep_slot >= 0) {
-        if ((st = ensure_slot(c, keep_slot, P.pw, frame_h))) return st;
-        if (!fld) {
-            HIP_OK(hipMemcpyAsync(c->slot[keep_slot][0], c->d_out, ys + 2 * cs, hipMemcpyDeviceToDevice, s));
-        } else {
-            // a field goes into its parity's rows of the slot's frame (the reference combines the
-            // two fields of a frame with dpb_combine_field_yuv, picture.cc:578-622); the other
-            // field's rows are left as they are
-            const int bot = P.h_pic.structure == H264R_BOTTOM_FIELD;
-            const size_t W = (size_t)P.pw * 16, Wc = W / 2;
-            HIP_OK(hipMemcpy2DAsync(c->slot[keep_slot][0] + bot * W, 2 * W, c->d_out, W, W, (size_t)P.ph * 16,
-                                    hipMemcpyDeviceToDevice, s));
-            for (int k = 1; k < 3; ++k)
-                HIP_OK(hipMemcpy2DAsync(c->slot[keep_slot][k] + bot * Wc, 2 * Wc, c->d_out + ys + (k - 1) * cs, Wc, Wc,
-                                        (size_t)P.ph * 8, hipMemcpyDeviceToDevice, s));
-        }
-    }
-    // planes and the device error word into this picture's pinned staging; the error word is
-    // cleared behind it, so each picture reports its own failures
-    HIP_OK(hipMemcpyAsync(P.out, c->d_out, ys + 2 * cs, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(P.out + ys + 2 * cs, c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemsetAsync(c->d_err, 0, sizeof(int), s));
-    HIP_OK(hipEventRecord(P.done, s));
-    P.pending = true;
-    ++c->sp_pending;
-    c->sp_fill = 1 - c->sp_fill;
-    return H264R_OK;
-}
-
-int h264r_picture_wait(h264r_ctx* c, uint8_t* y, uint8_t* u, uint8_t* v)
-{
-    if (!c) return H264R_EINVAL;
-    auto& P = c->sp[c->sp_wait];
-    if (!c->sp_pending || !P.pending) return H264R_ESTATE;
-    (void)hipSetDevice(c->device);
-    HIP_OK(hipEventSynchronize(P.done));
-    P.pending = false;
-    --c->sp_pending;
-    c->sp_wait = 1 - c->sp_wait;
-    const size_t n = (size_t)P.pw * P.ph, ys = n * 256, cs = chroma_bytes(c, P.pw, P.ph);
-    if (y) memcpy(y, P.out, ys);
-    if (u) memcpy(u, P.out + ys, cs);
-    if (v) memcpy(v, P.out + ys + cs, cs);
-    int e = 0;
-    memcpy(&e, P.out + ys + 2 * cs, sizeof(int));
-    return e ? H264R_EDEVICE : H264R_OK;
-}
-
-int h264r_picture_end(h264r_ctx* c, uint8_t* y, uint8_t* u, uint8_t* v, int keep_slot)
-{
-    if (!c) return H264R_EINVAL;
-    if (c->sp_pending) return H264R_ESTATE;        // collect the asynchronous pictures first
-    int st = h264r_picture_end_async(c, keep_slot);
-    if (st) return st;
-    return h264r_picture_wait(c, y, u, v);
-}
-
-}  // extern "C"
 
 #ifdef H264R_TRACE_INTRA
 // Diagnostic build only: copy the per-MB timing trace of k_intra_levels to the host.

@@ -1,0 +1,318 @@
+// host_output.hip -- the output stage of include/h264r_output.h on the host: the geometry and layout
+// of cropped, RGB and scaled RGB frames, and the launches of k_output.hip / k_output_scale.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "h264r.h"
+#include "h264r_output.h"
+#include "host_ctx.h"
+#include "kernels.h"
+
+// ------------------------------------------------------------- output stage (h264r_output.h)
+// The planes of one output frame: the geometry (output.cc:135-165) and the layout, as the job k_output
+// takes and, for the caller, as an h264r_out_geom.
+static int output_plan(int fmt, const h264r_out_desc* d, h264r_out_geom* g, h264r::OutJob* job)
+{
+    if (!d || fmt < 0 || fmt > 3 || d->width_mbs <= 0 || d->frame_height_mbs <= 0 ||
+        d->width_mbs > H264R_OUT_MAX_MBS || d->frame_height_mbs > H264R_OUT_MAX_MBS ||
+        (d->frame_mbs_only != 0 && d->frame_mbs_only != 1) ||
+        (d->layout != H264R_OUT_PLANAR && d->layout != H264R_OUT_SEMIPLANAR))
+        return H264R_EINVAL;
+    const int pa = d->pitch_align;
+    if (pa < 0 || pa > H264R_OUT_MAX_PITCH_ALIGN || (pa & (pa - 1))) return H264R_EINVAL;
+    if (d->crop_left < 0 || d->crop_right < 0 || d->crop_top < 0 || d->crop_bottom < 0) return H264R_EINVAL;
+    if (d->fake_chroma && fmt != 0) return H264R_EUNSUPPORTED;
+    const int sub_w = (fmt == 1 || fmt == 2) ? 2 : 1, sub_h = fmt == 1 ? 2 : 1;    // 4:0:0: CropUnitX 1
+    const int mb_cw = fmt ? 16 / sub_w : 0, mb_ch = fmt ? 16 / sub_h : 0;
+    const int64_t uy = 2 - d->frame_mbs_only;
+    const int64_t lc = d->crop_left, rc = d->crop_right, tc = d->crop_top * uy, bc = d->crop_bottom * uy;
+    const int64_t lw = 16 * (int64_t)d->width_mbs - sub_w * (lc + rc);
+    const int64_t lh = 16 * (int64_t)d->frame_height_mbs - sub_h * (tc + bc);
+    const int64_t cw = fmt ? mb_cw * (int64_t)d->width_mbs - (lc + rc) : 0;
+    const int64_t ch = fmt ? mb_ch * (int64_t)d->frame_height_mbs - (tc + bc) : 0;
+    if (lw <= 0 || lh <= 0 || (fmt && (cw <= 0 || ch <= 0))) return H264R_EINVAL;
+
+    h264r::OutJob J{};
+    auto plane = [&](int mode, int64_t w, int64_t h, int64_t x0, int64_t y0, int src_pitch) {
+        h264r::OutPlane& p = J.pl[J.nplanes];
+        p.off = J.nplanes ? J.pl[J.nplanes - 1].off + J.pl[J.nplanes - 1].pitch * J.pl[J.nplanes - 1].h : 0;
+        p.pitch = pa > 1 ? (w + pa - 1) / pa * pa : w;
+        p.w = (int32_t)w; p.h = (int32_t)h; p.x0 = (int32_t)x0; p.y0 = (int32_t)y0;
+        p.src_pitch = src_pitch; p.mode = mode;
+        ++J.nplanes;
+    };
+    plane(h264r::OUT_COPY_Y, lw, lh, sub_w * lc, sub_h * tc, 16 * d->width_mbs);
+    const bool semi = d->layout == H264R_OUT_SEMIPLANAR;
+    if (fmt) {
+        const int cp = mb_cw * d->width_mbs;
+        if (semi) plane(h264r::OUT_INTERLEAVE, 2 * cw, ch, lc, tc, cp);
+        else { plane(h264r::OUT_COPY_U, cw, ch, lc, tc, cp); plane(h264r::OUT_COPY_V, cw, ch, lc, tc, cp); }
+    } else if (d->fake_chroma) {
+        const int64_t fu = lw * lh / 4;                          // WriteUV (output.cc:205-224): one run per plane
+        if (fu > 0) {
+            if (semi) plane(h264r::OUT_FILL, 2 * fu, 1, 0, 0, 0);
+            else { plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); plane(h264r::OUT_FILL, fu, 1, 0, 0, 0); }
+        }
+    }
+    J.need_chroma = fmt != 0;
+    const h264r::OutPlane& last = J.pl[J.nplanes - 1];
+    const int64_t frame_bytes = last.off + last.pitch * last.h;
+    if (g) {
+        *g = h264r_out_geom{};
+        const int32_t l[4] = {(int32_t)(sub_w * lc), (int32_t)(sub_h * tc), (int32_t)lw, (int32_t)lh};
+        const int32_t cr[4] = {(int32_t)lc, (int32_t)tc, (int32_t)cw, (int32_t)ch};
+        for (int k = 0; k < 4; ++k) { g->luma[k] = l[k]; g->chroma[k] = fmt ? cr[k] : 0; }
+        for (int k = 0; k < J.nplanes; ++k) { g->plane_off[k] = J.pl[k].off; g->plane_pitch[k] = J.pl[k].pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) { *job = J; job->frame_stride = frame_bytes; }
+    return H264R_OK;
+}
+
+// The stream an output launch goes to: the caller's, or the context's.  The sources are, as a rule, what
+// the context's last launch wrote: ordered as run_batch orders launches.
+static int output_stream(h264r_ctx* c, void* stream, hipStream_t* s)
+{
+    (void)hipSetDevice(c->device);
+    *s = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    return h264r::order_after_last(c, *s);
+}
+
+int h264r_output_geometry(int chroma_format_idc, const h264r_out_desc* desc, h264r_out_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return output_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_out_frame* frames, int num_frames,
+                        uint8_t* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::OutJob job;
+    const int st = output_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.frame_stride = dst_frame_stride;
+    job.num_frames = num_frames;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    int items = 0;
+    for (int k = 0; k < job.nplanes; ++k)
+        items = std::max(items, job.pl[k].h * h264r::out_chunks_per_row(job.pl[k].w));
+    const int per = h264r::OUT_THREADS * h264r::OUT_ITEMS;
+    const dim3 grid((unsigned)((items + per - 1) / per), (unsigned)std::min(num_frames, 65535), (unsigned)job.nplanes);
+    hipLaunchKernelGGL(k_output, grid, dim3(h264r::OUT_THREADS), 0, s, job, frames, dst, c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- RGB frames (h264r_output.h)
+int h264r_rgb_coefficients(int matrix, int full_range, int32_t out[6])
+{
+    // floor(real * 2^14 + 1/2) of the header's reals: cy, crv, cgu, cgv, cbu, yo
+    static const int32_t rows[3][2][6] = {
+        {{19077, 26149, -6419, -13320, 33050, 16}, {16384, 22970, -5638, -11700, 29032, 0}},   // BT.601
+        {{19077, 29372, -3494, -8731, 34610, 16}, {16384, 25802, -3069, -7670, 30402, 0}},     // BT.709
+        {{19077, 27503, -3069, -10657, 35091, 16}, {16384, 24160, -2696, -9361, 30825, 0}},    // BT.2020
+    };
+    if (!out || matrix < H264R_CSC_BT601 || matrix > H264R_CSC_BT2020 || (full_range != 0 && full_range != 1))
+        return H264R_EINVAL;
+    for (int k = 0; k < 6; ++k) out[k] = rows[matrix][full_range][k];
+    return H264R_OK;
+}
+
+// The layout of one RGB frame of w x h pixels: for the caller as an h264r_rgb_geom, and as the output
+// side of the job the RGB kernels take.
+static void rgb_layout(int format, int64_t pa, int64_t w, int64_t h, h264r_rgb_geom* g, h264r::RgbJob* job)
+{
+    const bool planar = format == H264R_RGB_PLANAR_U8 || format == H264R_RGB_PLANAR_F16;
+    const int64_t bpp = format == H264R_RGB_PACKED_U8 ? 3 : format == H264R_RGB_PACKED_U8X4 ? 4 :
+                        format == H264R_RGB_PLANAR_F16 ? 2 : 1;
+    const int64_t pitch = pa > 1 ? (bpp * w + pa - 1) / pa * pa : bpp * w;
+    const int64_t frame_bytes = (planar ? 3 : 1) * pitch * h;
+    if (g) {
+        *g = h264r_rgb_geom{};
+        g->width = (int32_t)w; g->height = (int32_t)h;
+        for (int k = 0; k < (planar ? 3 : 1); ++k) { g->plane_off[k] = k * pitch * h; g->plane_pitch[k] = pitch; }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) {
+        for (int k = 0; k < 3; ++k) job->plane_off[k] = planar ? k * pitch * h : 0;
+        job->pitch = pitch;
+        job->frame_stride = frame_bytes;
+    }
+}
+
+// what both RGB entry points require of dst: room for every frame, and binary16 at even addresses
+static bool rgb_dst_ok(const h264r::RgbJob& job, const void* dst, int64_t dst_frame_stride)
+{
+    if (dst_frame_stride < job.frame_stride) return false;
+    return job.format != H264R_RGB_PLANAR_F16 || !((reinterpret_cast<uintptr_t>(dst) | (uint64_t)dst_frame_stride) & 1);
+}
+
+// What RGB frames are made from: the descriptor checked, the size of the cropped rectangle of desc->src
+// (known wherever the status is H264R_OK or H264R_EUNSUPPORTED) and the source side of the job: all of
+// it but the layout.
+static int rgb_source(int fmt, const h264r_rgb_desc* d, int32_t size[2], h264r::RgbJob* job)
+{
+    if (!d || d->src.layout != H264R_OUT_PLANAR || d->src.fake_chroma != 0) return H264R_EINVAL;
+    h264r_out_geom og;
+    const int st = output_plan(fmt, &d->src, &og, nullptr);
+    if (st != H264R_OK) return st;
+    size[0] = og.luma[2]; size[1] = og.luma[3];
+    if (d->matrix < H264R_CSC_BT601 || d->matrix > H264R_CSC_GBR ||
+        (d->chroma_up != H264R_UP_REPLICATE && d->chroma_up != H264R_UP_BILINEAR) ||
+        d->format < H264R_RGB_PACKED_U8 || d->format > H264R_RGB_PLANAR_F16 ||
+        (d->full_range != 0 && d->full_range != 1) || (d->bgr != 0 && d->bgr != 1) || d->alpha < 0 || d->alpha > 255)
+        return H264R_EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(d->scale[k]) || !std::isfinite(d->bias[k])) return H264R_EINVAL;
+    if (d->matrix == H264R_CSC_GBR && fmt != 3) return H264R_EUNSUPPORTED;
+
+    if (job) {
+        h264r::RgbJob J{};
+        J.lw = og.luma[2]; J.lh = og.luma[3]; J.x0 = og.luma[0]; J.y0 = og.luma[1];
+        J.cx0 = og.chroma[0]; J.cy0 = og.chroma[1]; J.cw = og.chroma[2]; J.ch = og.chroma[3];
+        J.lpitch = 16 * d->src.width_mbs;
+        J.cpitch = fmt == 3 ? J.lpitch : fmt ? J.lpitch / 2 : 0;
+        J.sub_h = fmt == 1 ? 2 : 1;
+        const bool bil = d->chroma_up == H264R_UP_BILINEAR;
+        J.mode = fmt == 0 ? h264r::RGB_MONO : fmt == 3 ? (d->matrix == H264R_CSC_GBR ? h264r::RGB_GBR : h264r::RGB_FULL) :
+                 !bil ? h264r::RGB_REP : fmt == 2 ? h264r::RGB_BIL1 : h264r::RGB_BIL2;
+        J.format = d->format; J.bgr = d->bgr; J.alpha = d->alpha;
+        if (d->matrix != H264R_CSC_GBR) {
+            int32_t k[6];
+            h264r_rgb_coefficients(d->matrix, d->full_range, k);
+            J.cy = k[0]; J.crv = k[1]; J.cgu = k[2]; J.cgv = k[3]; J.cbu = k[4]; J.yo = k[5];
+        }
+        for (int k = 0; k < 3; ++k) { J.scale[k] = d->scale[k]; J.bias[k] = d->bias[k]; }
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+// The layout of one RGB frame and the job k_output_rgb takes, from the geometry of desc->src.
+static int rgb_plan(int fmt, const h264r_rgb_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job)
+{
+    int32_t size[2];
+    const int st = rgb_source(fmt, d, size, job);
+    if (st == H264R_OK) rgb_layout(d->format, d->src.pitch_align, size[0], size[1], g, job);
+    return st;
+}
+
+int h264r_output_rgb_geometry(int chroma_format_idc, const h264r_rgb_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return rgb_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_rgb(h264r_ctx* c, const h264r_rgb_desc* desc, const h264r_out_frame* frames, int num_frames,
+                     void* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::RgbJob job;
+    const int st = rgb_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (!rgb_dst_ok(job, dst, dst_frame_stride)) return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.frame_stride = dst_frame_stride;
+    job.num_frames = num_frames;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    const int units = job.lh * h264r::rgb_units_per_row(job.lw);
+    const int per = h264r::RGB_THREADS * h264r::RGB_ITEMS;
+    const dim3 grid((unsigned)((units + per - 1) / per), (unsigned)std::min(num_frames, 65535));
+    hipLaunchKernelGGL(k_output_rgb, grid, dim3(h264r::RGB_THREADS), 0, s, job, frames, static_cast<uint8_t*>(dst),
+                       c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- scaled RGB frames (h264r_output.h)
+static int64_t gcd64(int64_t a, int64_t b)
+{
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    return a;
+}
+
+// The layout of one scaled frame and the job the k_output_rgb_scaled kernels take.  Argument errors come before
+// what is merely unsupported, as in rgb_source.
+static int scale_plan(int fmt, const h264r_scale_desc* d, h264r_rgb_geom* g, h264r::ScaleJob* job)
+{
+    if (!d) return H264R_EINVAL;
+    int32_t full[2];                                         // rgb_source knows the size before it finds GBR off 4:4:4
+    h264r::RgbJob R;
+    const int st = rgb_source(fmt, &d->rgb, full, &R);
+    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
+    if (d->roi_x < 0 || d->roi_y < 0 || d->roi_w < 0 || d->roi_h < 0 || (d->roi_w == 0) != (d->roi_h == 0) ||
+        d->out_w < 1 || d->out_w > H264R_SCALE_MAX_OUT || d->out_h < 1 || d->out_h > H264R_SCALE_MAX_OUT ||
+        (d->filter != H264R_SCALE_BILINEAR && d->filter != H264R_SCALE_AREA) || d->pad != 0)
+        return H264R_EINVAL;
+    const int64_t sw = d->roi_w ? d->roi_w : full[0], sh = d->roi_h ? d->roi_h : full[1];
+    if (d->roi_x + sw > full[0] || d->roi_y + sh > full[1]) return H264R_EINVAL;
+    if (st != H264R_OK) return st;
+    const int64_t gw = gcd64(sw, d->out_w), gh = gcd64(sh, d->out_h);
+    const int64_t rw = sw / gw, rh = sh / gh;
+    if (d->filter == H264R_SCALE_AREA && rw * rh > h264r::SCALE_AREA_MAX_T) return H264R_EUNSUPPORTED;
+
+    rgb_layout(d->rgb.format, d->rgb.src.pitch_align, d->out_w, d->out_h, g, &R);
+    if (job) {
+        h264r::ScaleJob J{};
+        J.rgb = R;
+        auto axis = [](int64_t S, int64_t D, int64_t gc) {
+            h264r::ScaleAxis a;
+            a.S = (int32_t)S; a.D = (int32_t)D; a.s = (int32_t)(S / gc); a.d = (int32_t)(D / gc);
+            a.inv_d = 1.0f / (float)a.d; a.inv_2D = 1.0f / (float)(2 * a.D);
+            return a;
+        };
+        J.ax = axis(sw, d->out_w, gw);
+        J.ay = axis(sh, d->out_h, gh);
+        J.roi_x = d->roi_x; J.roi_y = d->roi_y;
+        J.filter = d->filter;
+        // the widest window of columns: floor(d s / D) .. ceil((d + 1) s / D) holds ceil(s / D) + 1 at most
+        // (bilinear: 2), and one more in front where the unit starts on the even column before it
+        const int64_t span = (d->filter == H264R_SCALE_AREA ? (J.ax.s + J.ax.d - 1) / J.ax.d + 1 : 2) + (R.mode >= h264r::RGB_REP ? 1 : 0);
+        J.taps = (int32_t)std::min<int64_t>(span, h264r::RGB_UNIT);
+        J.T = (uint32_t)(rw * rh);
+        J.inv_2T = 1.0f / (2.0f * (float)J.T);
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+int h264r_output_rgb_scaled_geometry(int chroma_format_idc, const h264r_scale_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return scale_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h264r_out_frame* frames, int num_frames,
+                            void* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    h264r::ScaleJob job;
+    const int st = scale_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (!rgb_dst_ok(job.rgb, dst, dst_frame_stride)) return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    job.rgb.frame_stride = dst_frame_stride;
+    job.rgb.num_frames = num_frames;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    // the kernel of the job's mode and filter; frame z * grid.y + y, so that one launch holds any number
+    using ScaleKernel = void (*)(h264r::ScaleJob, const h264r_out_frame*, uint8_t*, int*);
+    ScaleKernel kernel[h264r::RGB_BIL2 + 1][2] = {};
+#define H264R_SCALE_KERNEL_ENTRY(NAME, MODE, FILTER) kernel[MODE][FILTER] = k_output_rgb_scaled_##NAME;
+    H264R_SCALE_KERNELS(H264R_SCALE_KERNEL_ENTRY)
+#undef H264R_SCALE_KERNEL_ENTRY
+    const int units = job.ay.D * h264r::rgb_units_per_row(job.ax.D);
+    const int gy = std::min(num_frames, 65535);
+    const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
+    hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
+                       static_cast<uint8_t*>(dst), c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}

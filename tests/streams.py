@@ -257,7 +257,7 @@ def frame_md5s(planes, cfg: dict) -> list[str]:
 
 
 def read_capture_file(path: str) -> list[dict]:
-    """Parse the raw capture written by oracle/h264r_cpu_abi.c (H264R_CAPTURE)."""
+    """Parse the raw capture written by oracle/h264r_cpu_abi.cc (H264R_CAPTURE)."""
     raw = open(path, "rb").read()
     off, pics = 0, []
     while off < len(raw):
