@@ -65,7 +65,7 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // k_inter4r: per 16-MB group of a workgroup, first the deblocking records DbInfo of the group's
 // MBs (dbinfo_block: their neighbour records and motion are loaded with the group's own record and
 // motion), then the reconstruction of its inter and I_PCM MBs (inter4_mbs); the records' registers
-// are dead before the motion compensation starts (125 VGPRs, 4 waves/SIMD).  Round 6 folded the
+// are dead before the motion compensation starts (127 VGPRs with both instantiations below, 4 waves/SIMD).  Round 6 folded the
 // records' own kernel (k_dbinfo, 1.2 ms per 1024 config-3 pictures at 8 waves/SIMD) into it:
 // config 3 11.96 -> 11.78 ms, config 4 4.64 -> 4.53 ms; all-intra config 2 13.87 -> 14.15 ms
 // (its records now run at 4 waves/SIMD; profiles/r06_e_fused_dbinfo_ab.txt).
@@ -80,6 +80,18 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // blockIdx.x % 8 (one eighth of the MB rows) of every picture: an XCD's motion
 // compensation reads only its band of the reference pictures (+ the MV reach), which its
 // 4 MB L2 holds, instead of every XCD streaming whole references through its L2.
+//
+// Two instantiations of the stages: a wave of a PLAIN picture (mb_inter4.h inter4_plain_picture: at most
+// INTER4_PLAIN_SLICES slices, each P or I with default weights -- every unweighted P picture, the bulk
+// of real Baseline and Main streams) that passes inter4_plain_wave takes the ones built for list 0
+// alone and no weighting (no list loop, no per-list copies and selects, no combine, only the
+// one-list records), every other wave the generic ones.  The workgroup classes its picture
+// from the slice headers its LDS fill holds (inter4_plain_mark); the branch is wave-uniform
+// and its two sides hold their registers apart (124 VGPRs the generic side, 91 the plain one).
+// As a kernel of its own the plain side runs at 5 waves/SIMD and 5.96 instead of 6.48 ms, but each
+// kernel then pays the dispatch of its workgroups for the other kernel's pictures, ~0.9 ns apiece:
+// 0.47 ms for 1024 plain 1080p pictures, 0.12 ms (2.5 % of the step) for config 4's 256, and several
+// pictures per workgroup spilled both kernels (profiles/r09_a_inter_plain_ab.txt).
 extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h264r_batch b, DbInfo* dbinfo, int2 rows,
                                                                                int* sp_flag, uint8_t* recon, int tag,
                                                                                int* zero, int nz, int* zero2, int nz2)
@@ -104,24 +116,43 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
     Inter4Pre pre = inter4_pre(b, g, pic, a0, aend, lane);
     DbNb nb = dbinfo_pre(b, g, pic, a0, aend, lane);
     const LdsRegs lr = inter4_lds_load(b, pic);
+    const int ns = (int)ld_const(&b.pics[pic].num_slices);
     db_tables_store(T, threadIdx.x, tv);
     inter4_lds_store(b, lr, S);
+    inter4_plain_mark(S, threadIdx.x, lr.hdr, ns);
     __syncthreads();
+    const bool plain = inter4_plain_picture(b, S, ns);
     for (;;) {
         if (a0 >= aend) return;
-        {
-            const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
-            // P pictures: the records without the list-1 motion words and with the one-list comparison
-            const bool one = (H264R_INTER_FAST & 2) && inter4_one_list(pre, nb);
-            uint2 m1 = inter4_no_list();
-            if (!one) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, pre.q.slice, 1);
-            if (!(H264R_INTER_DIAG & 32))
-                dbinfo_block(b, pic, inter4_lane(g, a0, aend, lane), S, T, pre.q, m0, m1,
-                             slice_hdr(slices, S, pre.q.slice), nb, dbinfo + (size_t)pic * g.nmb, one);
+        bool done = false;
+        // (the one-list records are H264R_INTER_FAST bit 2: without it no wave is a plain one)
+        if ((H264R_INTER_FAST & 2) && plain && inter4_plain_wave(pre, nb, ns)) {
+            const uint2 m0 = motion_word<true>(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
+            // (false, with no record written: an empty RefPicList entry -- the generic stages' after all)
+            done = (H264R_INTER_DIAG & 32) ||
+                   dbinfo_block<true>(b, pic, inter4_lane(g, a0, aend, lane), S, T, pre.q, m0, inter4_no_list(),
+                                      slice_hdr<true>(slices, S, pre.q.slice), nb, dbinfo + (size_t)pic * g.nmb, true);
+            if (done) {
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                inter4_mbs<true>(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+            }
         }
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+        if (!done) {
+            {
+                const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
+                // P pictures: the records without the list-1 motion words and with the one-list comparison
+                const bool one = (H264R_INTER_FAST & 2) && inter4_one_list(pre, nb);
+                uint2 m1 = inter4_no_list();
+                if (!one) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, pre.q.slice, 1);
+                if (!(H264R_INTER_DIAG & 32))
+                    dbinfo_block(b, pic, inter4_lane(g, a0, aend, lane), S, T, pre.q, m0, m1,
+                                 slice_hdr(slices, S, pre.q.slice), nb, dbinfo + (size_t)pic * g.nmb, one);
+            }
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+        }
         if (++grp >= gend) return;
         a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;
         int ln2 = lane;

@@ -53,12 +53,15 @@ namespace h264r {
 
 constexpr int INTER4_MBS = 16;   // MBs per 256-thread workgroup (4 waves x 4)
 constexpr int INTER4_LDS_SLICES = 64;   // slices whose ref tables the workgroup keeps in LDS
+constexpr int INTER4_PLAIN_SLICES = 8;  // slices of a plain picture at most (inter4_plain_picture)
+static_assert(INTER4_PLAIN_SLICES <= INTER4_LDS_SLICES, "a plain picture's slices are all in the LDS copy");
 
 struct Inter4Lds {
     const uint8_t* planes[3 * H264R_MAX_SLOTS];
     uint2 hdr[INTER4_LDS_SLICES];                            // dwords 0..1 of the picture's slices (type, idc, offsets, wp)
     int8_t ref_slot[INTER4_LDS_SLICES][2][H264R_MAX_REFS];   // h264r_slice::ref_slot of the picture's slices
     uint8_t slice_type[INTER4_LDS_SLICES];                   // h264r_slice::slice_type of the same slices
+    uint8_t not_plain[INTER4_PLAIN_SLICES];                  // slice i keeps the picture from being plain (inter4_plain_picture)
 };
 
 // A lane's roles ("Lane roles" above) for the MBs a0 .. a0+3 of a picture.
@@ -98,25 +101,32 @@ DEV int slice_byte(const h264r_slice* slices, int slice, int off)
                                                                         (int)sizeof(h264r_slice), 0x00020000);
     return __builtin_amdgcn_raw_buffer_load_b8(rs, off, 0, 0);
 }
+// NEAR (a template parameter of the three readers below and of the stages that call them): every
+// slice index the caller passes is below INTER4_LDS_SLICES, so the LDS copy answers alone and the
+// slice-table path is not compiled (the PLAIN stages: a plain picture has at most INTER4_PLAIN_SLICES).
 // slice_type of a slice: the LDS copy, else the slice table
+template <bool NEAR = false>
 DEV int slice_type_of(const h264r_slice* slices, const Inter4Lds& S, int slice)
 {
     int t = S.slice_type[min(slice, INTER4_LDS_SLICES - 1)];
-    if (slice >= INTER4_LDS_SLICES) t = slice_byte(slices, slice, (int)offsetof(h264r_slice, slice_type));
+    if constexpr (!NEAR)
+        if (slice >= INTER4_LDS_SLICES) t = slice_byte(slices, slice, (int)offsetof(h264r_slice, slice_type));
     return t;
 }
 
 // Dwords 0..1 of slice `slice` (type, idc, filter offsets, wp mode, log2 wd): the LDS copy,
 // else the slice table
+template <bool NEAR = false>
 DEV uint2 slice_hdr(const h264r_slice* slices, const Inter4Lds& S, int slice)
 {
-    if (slice < INTER4_LDS_SLICES) return S.hdr[slice];
+    if (NEAR || slice < INTER4_LDS_SLICES) return S.hdr[NEAR ? min(slice, INTER4_LDS_SLICES - 1) : slice];
     return *reinterpret_cast<const uint2*>(&slices[slice]);
 }
 
 // Motion of one 4x4 block as {mv, ref_idx | slot << 8} per list: RefPicList[l][ref_idx]
 // of the block's slice resolved to its DPB slot (get_ref_pic dpb.cc:1046-1054;
 // pic_motion_params::ref_pic interpret_mb.cc:611-623), slot -1 when the list is unused.
+template <bool NEAR = false>
 DEV uint2 motion_word(uint32_t mv, int ri, const h264r_slice* slices, const Inter4Lds& S, int slice, int l)
 {
     // the table read at a clamped index and the "no list" case selected afterwards: an LDS
@@ -124,8 +134,9 @@ DEV uint2 motion_word(uint32_t mv, int ri, const h264r_slice* slices, const Inte
     const bool has = ri >= 0 && ri < H264R_MAX_REFS;
     const int ric = has ? ri : 0;
     int slot = S.ref_slot[min(slice, INTER4_LDS_SLICES - 1)][l][ric];
-    if (slice >= INTER4_LDS_SLICES)
-        slot = (int8_t)slice_byte(slices, slice, (int)offsetof(h264r_slice, ref_slot) + l * H264R_MAX_REFS + ric);
+    if constexpr (!NEAR)
+        if (slice >= INTER4_LDS_SLICES)
+            slot = (int8_t)slice_byte(slices, slice, (int)offsetof(h264r_slice, ref_slot) + l * H264R_MAX_REFS + ric);
     slot = has ? slot : -1;
     return make_uint2(mv, (uint32_t)(uint8_t)ri | ((uint32_t)(uint8_t)slot << 8));
 }
@@ -532,6 +543,36 @@ DEV bool inter4_one_list(const Inter4Pre& pre, const DbNb& nb)
     return !__any(used);
 }
 
+// A picture is PLAIN when it has at most INTER4_PLAIN_SLICES slices, each of them P or I with
+// default weights (wp_mode 0): its waves may take the PLAIN stages.  The workgroup works it out
+// beside its LDS fill, whose first threads hold the slice headers anyway: thread t < 8 marks slice t
+// (inter4_plain_mark, before the barrier), every wave reads the 8 marks back after it.
+// n: the picture's num_slices.
+static_assert(offsetof(Inter4Lds, not_plain) % 8 == 0 && INTER4_PLAIN_SLICES == 8, "the marks are read as one uint2");
+DEV void inter4_plain_mark(Inter4Lds& S, int t, uint2 hdr, int n)
+{
+    const uint32_t type = hdr.x & 255, wp = hdr.y & 255;                            // slice_type, wp_mode
+    if (t < INTER4_PLAIN_SLICES) S.not_plain[t] = t < n && ((type != H264R_SLICE_P && type != H264R_SLICE_I) || wp != 0);
+}
+DEV bool inter4_plain_picture(const h264r_batch& b, const Inter4Lds& S, int n)
+{
+    const uint2 m = *reinterpret_cast<const uint2*>(S.not_plain);
+    return n >= 1 && n <= min(b.slice_stride, INTER4_PLAIN_SLICES) && __builtin_amdgcn_readfirstlane(m.x | m.y) == 0;
+}
+// What a wave of a plain picture must find before it takes the PLAIN stages; a wave that does not
+// takes the generic stages instead (k_recon.hip k_inter4r).  No conforming stream fails it:
+//   - inter4_one_list: the one-list records, and list 0 alone in the prediction;
+//   - every slice index in reach (mine, my left and upper MB's) is one of the picture's ns slices,
+//     which inter4_plain_picture vouches for (and so in the LDS copy);
+//   - every block of an inter MB has a list-0 ref_idx (the generic path predicts a block without
+//     one from list 1: zeros).
+DEV bool inter4_plain_wave(const Inter4Pre& pre, const DbNb& nb, int ns)
+{
+    const bool far = (int)pre.q.slice >= ns || (int)nb.L.slice >= ns || (int)nb.U.slice >= ns;
+    const bool noref = !mb_is_intra(pre.q) && pre.ri[0] < 0;
+    return inter4_one_list(pre, nb) && !__any(far || noref);
+}
+
 // The record of dbinfo_block once the motion of the block (mq), of its left (ml) and of its upper
 // neighbour (mu) is resolved.  ONE: the wave compares one list (bs_compare_one).
 template <bool ONE>
@@ -600,7 +641,11 @@ DEV void dbinfo_records(const h264r_mb& q, const h264r_mb& L, const h264r_mb& U,
 // k_inter4r, before the group's reconstruction.
 // `one` (wave-uniform, inter4_one_list): no list-1 motion in reach of any lane; m1 is then
 // inter4_no_list().
-DEV void dbinfo_block(const h264r_batch& b, int pic, const Inter4Lane& ln, const Inter4Lds& S, const DbTables& T,
+// PLAIN (a plain wave of k_inter4r): `one` holds and every slice is in the LDS copy, so only the one-list records are
+// compiled.  Returns false, with nothing written, when the wave needs bs_compare after all: the
+// caller runs the generic instantiation instead.  The generic instantiation always returns true.
+template <bool PLAIN = false>
+DEV bool dbinfo_block(const h264r_batch& b, int pic, const Inter4Lane& ln, const Inter4Lds& S, const DbTables& T,
                       const h264r_mb& q, uint2 m0, uint2 m1, uint2 qsh, const DbNb& nb, DbInfo* __restrict__ dbout, bool one)
 {
     const int bx = ln.bx, by = ln.by;
@@ -610,30 +655,42 @@ DEV void dbinfo_block(const h264r_batch& b, int pic, const Inter4Lane& ln, const
     const h264r_mb& U = nb.U;
     // the neighbour block belongs to this MB or to the left / upper one (its slice resolves it)
     const int lsl = bx > 0 ? q.slice : L.slice, usl = by > 0 ? q.slice : U.slice;
-    const uint2 l0 = motion_word(nb.lmv[0], nb.lri[0], slices, S, lsl, 0), u0 = motion_word(nb.umv[0], nb.uri[0], slices, S, usl, 0);
+    const uint2 l0 = motion_word<PLAIN>(nb.lmv[0], nb.lri[0], slices, S, lsl, 0);
+    const uint2 u0 = motion_word<PLAIN>(nb.umv[0], nb.uri[0], slices, S, usl, 0);
     uint2 l1 = inter4_no_list(), u1 = l1;
-    if (!one) {
-        l1 = motion_word(nb.lmv[1], nb.lri[1], slices, S, lsl, 1);
-        u1 = motion_word(nb.umv[1], nb.uri[1], slices, S, usl, 1);
+    if constexpr (!PLAIN) {
+        if (!one) {
+            l1 = motion_word(nb.lmv[1], nb.lri[1], slices, S, lsl, 1);
+            u1 = motion_word(nb.umv[1], nb.uri[1], slices, S, usl, 1);
+        }
     }
-    const int l_type = slice_type_of(slices, S, L.slice), u_type = slice_type_of(slices, S, U.slice);
+    const int l_type = slice_type_of<PLAIN>(slices, S, L.slice), u_type = slice_type_of<PLAIN>(slices, S, U.slice);
     // field pictures: mvlimit 2 (deblock.cc:86,164) and no bS 4 across horizontal MB edges
     // (cond_bS4 = !field || vertical, deblock.cc:103-107,184-189)
     const int fld = (int)__builtin_amdgcn_readfirstlane(ld_const(&b.pics[pic].structure)) != H264R_FRAME;
     // ---- deblocking record (Deblock::strength deblock.cc:78-289): this lane's
     // left edge (vertical edge bx, segment by) and top edge (horizontal edge by,
     // segment bx)
-    if (ln.valid) {
-        const MotionRef mq = motion_of(m0, m1), ml = motion_of(l0, l1), mu = motion_of(u0, u1);
-        // bs_compare_one also needs a list-0 reference on one side of every edge it is asked about.
-        // Only edges between two inter MBs reach the comparison, so an inter MB's block without one
-        // (no conforming stream has it: ref_idx out of range, or an empty RefPicList entry) sends
-        // the wave to bs_compare.
-        if (one) one = !__any(!mb_is_intra(q) && mq.ref[0] < 0 && (ml.ref[0] < 0 || mu.ref[0] < 0));
-        DbInfo* out = dbout + ln.aa;
-        if (one) dbinfo_records<true>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
-        else dbinfo_records<false>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+    const MotionRef mq = motion_of(m0, m1), ml = motion_of(l0, l1), mu = motion_of(u0, u1);
+    // bs_compare_one also needs a list-0 reference on one side of every edge it is asked about.
+    // Only edges between two inter MBs reach the comparison, so an inter MB's block without one
+    // (no conforming stream has it: ref_idx out of range, or an empty RefPicList entry) sends
+    // the wave to bs_compare.
+    const bool both_missing = !mb_is_intra(q) && mq.ref[0] < 0 && (ml.ref[0] < 0 || mu.ref[0] < 0);
+    if constexpr (PLAIN) {
+        if (__any(ln.valid && both_missing)) return false;
     }
+    if (ln.valid) {
+        DbInfo* out = dbout + ln.aa;
+        if constexpr (PLAIN) {
+            dbinfo_records<true>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+        } else {
+            if (one) one = !__any(both_missing);
+            if (one) dbinfo_records<true>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+            else dbinfo_records<false>(q, L, U, mq, ml, mu, ln.blk, hasL, hasU, qsh.x, l_type, u_type, fld, T, out);
+        }
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------ the stages of inter4_mbs
@@ -652,68 +709,87 @@ DEV void inter4_pcm(uint8_t* rmb, const Inter4Lane& L, const int16_t* lv)
                 *reinterpret_cast<const uint16_t*>(raw + 256 + pl * 64 + (L.by * 2 + r) * 8 + L.bx * 2);
 }
 
+// The motion compensation of my block from one list (mw: its motion_word; rr: its ref_idx): tY[i] luma
+// row i's four samples as bytes, tC[pl] my 2x2 chroma samples of plane pl (chroma_block_pred2); 128
+// (no_ref, inter_prediction.cc:164-167,366-369) where the list's entry names no picture.  `use`: the
+// lane predicts from this list at all.  structure / fld: the picture's, wave-uniform.
+DEV void inter4_mc(const Geom& g, const Inter4Lane& L, const Inter4Lds& S, int structure, int fld, uint2 mw, int rr, bool use,
+                   uint32_t (&tY)[4], uint32_t (&tC)[2])
+{
+    tY[0] = tY[1] = tY[2] = tY[3] = 0x80808080u;
+    tC[0] = tC[1] = 0x80808080u;
+    const int ref = (int8_t)((mw.y >> 8) & 255);                // slot | H264R_REF_BOTTOM
+    const int slot = ref & 31, bot = fld & (ref >> 6);
+    const bool ok = use && ref >= 0 && (ref & ~H264R_REF_BOTTOM) < H264R_MAX_SLOTS && rr < H264R_MAX_REFS &&
+                    S.planes[slot * 3];
+    const int mvx = (int16_t)(mw.x & 0xFFFF), mvy = (int16_t)(mw.x >> 16);
+    const int vx = L.X4 * 16 + mvx, vy = L.Y4 * 16 + mvy;       // quarter luma / eighth chroma units
+    const int x = vx >> 2, y = vy >> 2;
+    {
+        // the 9 window rows of the lane's own block, straight from the plane
+        uint32_t w[9][3];
+        if constexpr (H264R_INTER_DIAG & 4) {
+            // diagnostic build (wrong output): no window loads, no luma filter
+            tY[0] = tY[1] = tY[2] = tY[3] = (uint32_t)(vx ^ vy);
+        } else {
+            if (ok) luma_window_global(S.planes[slot * 3] + bot * g.W, g.W, g.W << fld, g.H, x, y, w);
+            if constexpr (H264R_INTER_DIAG & 2) {
+                // diagnostic build (wrong output): the window loads without the luma filter
+                if (ok) {
+                    uint32_t acc = 0;
+#pragma unroll
+                    for (int r = 0; r < 9; ++r) acc ^= w[r][0] ^ w[r][1] ^ w[r][2];
+                    tY[0] = tY[1] = tY[2] = tY[3] = acc;
+                }
+            } else {
+                if (ok) luma_block_pred(w, g.W, x, vx & 3, vy & 3, tY);
+            }
+        }
+    }
+    // a reference field of the other parity: the chroma sample grid sits a quarter
+    // chroma row off (get_block_chroma inter_prediction.cc:352-355)
+    const int vyc = vy + (fld && bot != (structure == H264R_BOTTOM_FIELD) ? (bot ? -2 : 2) : 0);
+    if constexpr (H264R_INTER_DIAG & 8) {
+        tC[0] = tC[1] = (uint32_t)vyc;        // diagnostic build (wrong output): no chroma MC
+    } else {
+        if (ok) chroma_block_pred2(S.planes[slot * 3 + 1] + bot * g.Wc, S.planes[slot * 3 + 2] + bot * g.Wc, g.Wc,
+                                   g.Wc << fld, g.Hc, vx >> 3, vyc >> 3, vx & 7, vyc & 7, tC);
+    }
+}
+
 // The prediction of my block: the motion compensation of each list it uses (m0 / m1: motion_word),
 // combined by the slice's weighted prediction (qs, wp_mode).  predY[i]: luma row i's four samples as
 // bytes; predC[pl]: my 2x2 chroma samples of plane pl (chroma_block_pred2).
+// PLAIN (a plain wave of k_inter4r): the caller's lanes all predict from list 0 alone with default weights, so the
+// prediction is list 0's motion compensation: no list loop, no per-list copies, no combine.
+template <bool PLAIN = false>
 DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inter4Lane& L, const Inter4Lds& S,
                         const h264r_slice* __restrict__ qs, int wp_mode, uint2 m0, uint2 m1, uint32_t (&predY)[4],
                         uint32_t (&predC)[2])
 {
-    const int r0 = (int8_t)(m0.y & 255), r1 = (int8_t)(m1.y & 255);
-    const int dir = (r0 >= 0 && r1 >= 0) ? 2 : (r0 >= 0 ? 0 : 1);
-    // the prediction of each list in named registers: an array indexed by the (not
-    // unrolled) list loop was promoted to LDS by the compiler (48 B per lane)
-    uint32_t pY[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, pC[2][2] = {{0, 0}, {0, 0}};
     // a field picture (include/h264r.h H264R_TOP_FIELD) reads fields of the DPB frames:
     // every second row from the field's first row, clamped to the field's own rows
     const int structure = (int)__builtin_amdgcn_readfirstlane(ld_const(&b.pics[pic].structure));
     // an MBAFF picture of a mixed batch counts as a field picture here and in dbinfo_block
     const int fld = structure != H264R_FRAME;
+    const int r0 = (int8_t)(m0.y & 255);
+    if constexpr (PLAIN) {
+        inter4_mc(g, L, S, structure, fld, m0, r0, true, predY, predC);
+        return;
+    }
+    const int r1 = (int8_t)(m1.y & 255);
+    const int dir = (r0 >= 0 && r1 >= 0) ? 2 : (r0 >= 0 ? 0 : 1);
+    // the prediction of each list in named registers: an array indexed by the (not
+    // unrolled) list loop was promoted to LDS by the compiler (48 B per lane)
+    uint32_t pY[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, pC[2][2] = {{0, 0}, {0, 0}};
 #pragma unroll 1
     for (int l = 0; l < 2; ++l) {
         const uint2 mw = l ? m1 : m0;
         const int rr = l ? r1 : r0;
         const bool use = rr >= 0;
         if (!__any(use)) continue;                                  // P pictures: list 1 never
-        uint32_t tY[4] = {0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
-        uint32_t tC[2] = {0x80808080u, 0x80808080u};                // no_ref: 128 (inter_prediction.cc:164-167,366-369)
-        const int ref = (int8_t)((mw.y >> 8) & 255);                // slot | H264R_REF_BOTTOM
-        const int slot = ref & 31, bot = fld & (ref >> 6);
-        const bool ok = use && ref >= 0 && (ref & ~H264R_REF_BOTTOM) < H264R_MAX_SLOTS && rr < H264R_MAX_REFS &&
-                        S.planes[slot * 3];
-        const int mvx = (int16_t)(mw.x & 0xFFFF), mvy = (int16_t)(mw.x >> 16);
-        const int vx = L.X4 * 16 + mvx, vy = L.Y4 * 16 + mvy;       // quarter luma / eighth chroma units
-        const int x = vx >> 2, y = vy >> 2;
-        {
-            // the 9 window rows of the lane's own block, straight from the plane
-            uint32_t w[9][3];
-            if constexpr (H264R_INTER_DIAG & 4) {
-                // diagnostic build (wrong output): no window loads, no luma filter
-                tY[0] = tY[1] = tY[2] = tY[3] = (uint32_t)(vx ^ vy);
-            } else {
-                if (ok) luma_window_global(S.planes[slot * 3] + bot * g.W, g.W, g.W << fld, g.H, x, y, w);
-                if constexpr (H264R_INTER_DIAG & 2) {
-                    // diagnostic build (wrong output): the window loads without the luma filter
-                    if (ok) {
-                        uint32_t acc = 0;
-#pragma unroll
-                        for (int r = 0; r < 9; ++r) acc ^= w[r][0] ^ w[r][1] ^ w[r][2];
-                        tY[0] = tY[1] = tY[2] = tY[3] = acc;
-                    }
-                } else {
-                    if (ok) luma_block_pred(w, g.W, x, vx & 3, vy & 3, tY);
-                }
-            }
-        }
-        // a reference field of the other parity: the chroma sample grid sits a quarter
-        // chroma row off (get_block_chroma inter_prediction.cc:352-355)
-        const int vyc = vy + (fld && bot != (structure == H264R_BOTTOM_FIELD) ? (bot ? -2 : 2) : 0);
-        if constexpr (H264R_INTER_DIAG & 8) {
-            tC[0] = tC[1] = (uint32_t)vyc;        // diagnostic build (wrong output): no chroma MC
-        } else {
-            if (ok) chroma_block_pred2(S.planes[slot * 3 + 1] + bot * g.Wc, S.planes[slot * 3 + 2] + bot * g.Wc, g.Wc,
-                                       g.Wc << fld, g.Hc, vx >> 3, vyc >> 3, vx & 7, vyc & 7, tC);
-        }
+        uint32_t tY[4], tC[2];
+        inter4_mc(g, L, S, structure, fld, mw, rr, use, tY, tC);
         const bool l1 = l != 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1152,6 +1228,10 @@ DEV void inter4_store_chroma(uint8_t* rmb, const Inter4Lane& L, const uint32_t (
 // The inter / I_PCM macroblocks a0 .. a0+3 of picture `pic` (k_inter4r; their deblocking records come
 // first, dbinfo_block).  Inter MBs of SP slices are left out and flagged in *sp_flag (the launch
 // tag): k_inter_sp's (mb_inter_sp.h).
+// PLAIN: a wave of a plain picture (inter4_plain_picture) that passed inter4_plain_wave --
+// P and I slices in the LDS copy, default weights, list 0 alone: no SP test, no list-1 motion word,
+// and inter4_predict's one-list form.
+template <bool PLAIN = false>
 DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int aend, int lane,
                     const Inter4Lds& S, int* sp_flag, const Inter4Pre& pre, uint8_t* __restrict__ recon, int tag)
 {
@@ -1162,17 +1242,19 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
     // MB record (inter4_pre: two 16-byte loads -- a struct copy becomes one byte load per field,
     // each waited on its own), its slice header and the motion of this block
     const h264r_mb q = pre.q;
-    const uint2 qsh = slice_hdr(slices, S, q.slice);
-    const uint2 m0 = motion_word(pre.mv[0], pre.ri[0], slices, S, q.slice, 0);
-    const uint2 m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, q.slice, 1);
+    const uint2 qsh = slice_hdr<PLAIN>(slices, S, q.slice);
+    const uint2 m0 = motion_word<PLAIN>(pre.mv[0], pre.ri[0], slices, S, q.slice, 0);
+    uint2 m1 = inter4_no_list();
+    if constexpr (!PLAIN) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, q.slice, 1);
 
     const bool pcm = q.mb_type == H264R_I_PCM;
     if (!L.valid || (mb_is_intra(q) && !pcm)) return;                // intra: k_intra_* (lanes idle here)
-    if ((qsh.x & 255) == H264R_SLICE_SP && !mb_is_intra(q)) { *sp_flag = tag; return; }   // k_inter_sp's
+    if constexpr (!PLAIN)
+        if ((qsh.x & 255) == H264R_SLICE_SP && !mb_is_intra(q)) { *sp_flag = tag; return; }   // k_inter_sp's
     if (pcm) { inter4_pcm(recon_mb(recon, g, pic, L.aa), L, b.levels + q.coef_off); return; }
 
     uint32_t predY[4], predC[2];
-    inter4_predict(b, g, pic, L, S, &slices[q.slice], qsh.y & 255, m0, m1, predY, predC);
+    inter4_predict<PLAIN>(b, g, pic, L, S, &slices[q.slice], qsh.y & 255, m0, m1, predY, predC);
     // What only the residual and the stores read comes after the motion compensation, so that it is
     // not live across it: the residual inputs (30 VGPRs: k_inter4r fits 128 VGPRs = 4 waves/SIMD;
     // config 3 475 -> 493 M MB/s, profiles/r03_h_inter_ab.txt) and the two 64-bit addresses (formed
