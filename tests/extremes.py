@@ -23,6 +23,13 @@ Families (case names in CASES):
   S  strength from motion (tests/extremes_s.py): one-dimensional pictures without residual whose edges
      are decided by the motion comparison alone, every row of that rule (limits per component, picture
      identity against ref_idx, both pairings of two lists, slice boundaries) on its thresholds
+  I  intra prediction (tests/extremes_i.py): intra MBs without residual whose neighbours are I_PCM
+     MBs with crafted samples or, under constrained_intra_pred, inter MBs that leave poison behind:
+     every legal (mode, block, availability) of I_4x4, I_8x8, I_16x16 and chroma (4:2:0 and 4:2:2) with
+     random neighbours, value patterns, DC sums on both sides of every rounding, the plane predictors
+     at +-9180 / +-2550 and clipping at both ends; picture borders, slice boundaries, a chain of
+     dependency levels 1..7, field pictures, and a generated MBAFF case with its levels zeroed; checked
+     against a restatement of 8.3 in Python integers with a mutation check per cell
 tests/test_extremes.py holds the census (each family hits its target, from the inputs and the oracle
 alone) and pins the oracle to the reference decoder on these inputs (tests/golden/extremes.json);
 tests/test_gpu_extremes.py compares the GPU with the oracle.
@@ -1606,3 +1613,9 @@ import extremes_s as _S  # noqa: E402  (the builders need the helpers above)
 
 CASES.update(_S.S_CASES)
 S_CASES = list(_S.S_CASES)
+
+# ---------------------------------------------------------------- I: intra prediction
+import extremes_i as _I  # noqa: E402
+
+CASES.update(_I.I_CASES)
+I_CASES = list(_I.I_CASES)

@@ -2,7 +2,7 @@
 """Generate tests/golden/extremes.json from the compiled REFERENCE decoder: the directed
 extreme-value cases of tests/extremes.py (residuals at the packed transforms' bound, 0 / 255
 reference patterns, motion vectors at the limits and across every border, extreme explicit
-weights, deblocking lines on the thresholds).
+weights, deblocking lines on the thresholds, strength from motion, directed intra prediction).
 
 Run where the reference sources are (the GPU box never has them):
 

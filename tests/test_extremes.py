@@ -18,6 +18,7 @@ import pytest
 
 import _oracle as O
 import extremes as X
+import extremes_i as I
 from h264r import _abi as A
 from h264r import synth
 
@@ -551,3 +552,256 @@ def test_census_s_mbaff():
         for sg in (1, -1):
             assert {(sg, 0, 0), (sg, 0, 1)} <= live_rows[(2, fld)] and {(0, sg, 0), (0, sg, 1)} <= live_rows[(3, fld)]
             assert any(sx == sg and b == 0 for sx, _, b in live_rows[(4, fld)]) and any(sy == sg and b == 1 for _, sy, b in live_rows[(4, fld)])
+
+
+# ---------------------------------------------------------------- census: I
+def _i_tags(name):
+    return {(s["pic"], s["mb"]): s for s in X.build(name).info["sites"]}
+
+
+@pytest.mark.parametrize("name", I.I_RESTATED)
+def test_census_i_restated(name):
+    """Intra prediction restated (extremes_i.intra_restate: 8.3 in Python integers, availability by
+    6.4.12 from the records alone) equals the oracle's reconstruction of every picture byte for byte;
+    the output is the reconstruction (deblock_idc 1 everywhere); every intra MB is without residual
+    unless it is in the chain; every site stands alone at dependency level 1; and the availability
+    bits the restatement derived for each block are the ones the block geometry (avail4 / avail8) gives for the mask
+    its builder designed."""
+    c = X.build(name)
+    entries, equal = I.census(name)
+    assert all(equal), (name, equal)
+    tags = _i_tags(name)
+    for pi, p in enumerate(c.pics):
+        assert all(int(s["deblock_idc"]) == 1 for s in p.slices)
+        assert all(np.array_equal(a, b) for a, b in zip(O.decode(p, c.refs), O.decode(p, c.refs, stage="recon")))
+        lv = I.levels_of(p)
+        W = p.cfg.width_mbs
+        for a, m in enumerate(p.mbs):
+            if int(m["flags"]) & A.MBF_INTRA and int(m["mb_type"]) != A.I_PCM:
+                s = tags[(pi, (a % W, a // W))]
+                assert s["tag"] == "chain" or (int(m["cbp"]) == 0 and int(m["cbp_blks"]) == 0 and lv[a // W, a % W] == 1)
+    for e in entries:
+        mask = tags[(e["pic"], e["mb"])]["mask"]
+        if e["kind"] in ("i4", "i8"):
+            want = (I.avail4 if e["kind"] == "i4" else I.avail8)(e["blk"], mask)
+            got = e["bits"]
+            assert (got[0], got[1], got[3]) == (want[0], want[1], want[3]) and (not got[1] or got[2] == want[2]), (name, e["mb"], e["blk"])
+        else:
+            assert e["bits"] == (mask[0], mask[1], mask[3])
+
+
+def _i_random_entries(names):
+    """The logged blocks of the sites whose neighbours are seeded random bytes."""
+    out = []
+    for n in names:
+        tags = _i_tags(n)
+        out += [e for e in I.census(n)[0] if tags[(e["pic"], e["mb"])]["tag"] in ("mask", "border", "slice", "chain")]
+    return out
+
+
+def _i_cells(entries, chroma_blocks):
+    """Per kind (required cells, cells hit): a cell is hit when, among its blocks with random
+    neighbours, one changes under EVERY other legal mode and, for each availability bit the mode
+    reads, one changes when that bit is flipped (the poison, or the other sum, comes into play).  A
+    flip of a bit the mode does not read must change nothing, anywhere."""
+    req = I.required_cells(chroma_blocks)
+    modes_ok = {k: set() for k in req}
+    flips_ok = {k: {} for k in req}
+    need = {k: {} for k in req}
+    for e in entries:
+        kind, mode, bits = e["kind"], e["mode"], e["bits"]
+        group = kind if kind in ("i4", "i8", "i16") else "c"
+        cell = I.cell_of(e)
+        assert cell in req[group], (group, cell)
+        rd = I.reads(kind, mode, bits)
+        if not (group == "c" and mode == 0):
+            for i, changed in e["flips"].items():
+                assert i in rd or not changed, (kind, mode, bits, i)
+        need[group].setdefault(cell, set()).update(i for i in rd)
+        if e["others"]:
+            modes_ok[group].add(cell)
+        for i in rd:
+            if e["flips"].get(i):
+                flips_ok[group].setdefault(cell, set()).add(i)
+        if group == "c" and mode == 0:
+            for blk, _, _ in e["blocks"]:
+                xO, yO = (blk & 1) * 4, (blk >> 1) * 4
+                dcell = (kind, blk, bits[0], bits[1])
+                use = I.chroma_dc_uses(xO, yO, bits[0], bits[1])
+                if e["blk_others"][blk]:
+                    modes_ok["cdc"].add(dcell)
+                for i in (0, 1):
+                    nb = (bits[0] ^ (i == 0), bits[1] ^ (i == 1))
+                    eff = I.chroma_dc_uses(xO, yO, *nb) != use
+                    if i in e["blk_flips"]:
+                        assert eff or not e["blk_flips"][i][blk], (dcell, i)
+                        if eff:
+                            need["cdc"].setdefault(dcell, set()).add(i)
+                            if e["blk_flips"][i][blk]:
+                                flips_ok["cdc"].setdefault(dcell, set()).add(i)
+    hit = {k: {c for c in req[k] if c in modes_ok[k] and flips_ok[k].get(c, set()) >= need[k].get(c, set())} for k in req}
+    return req, hit
+
+
+def test_census_i_cells():
+    """Every (mode, block, availability) cell the legality rules and the block geometry allow occurs
+    in the plain 4:2:0 cases with random neighbours, and every such cell passes the mutation check."""
+    req, hit = _i_cells(_i_random_entries(I.I_PLAIN), 4)
+    for k in req:
+        print(f"I census {k}: required {len(req[k])} hit {len(hit[k])}")
+    for k in req:
+        assert hit[k] == req[k], (k, sorted(req[k] - hit[k])[:8])
+    assert {k: len(v) for k, v in req.items()} == I.CELL_COUNTS
+
+
+def test_census_i_422():
+    """The 4:2:2 chroma predictor: every (mode, availability) cell of both planes and every DC cell of
+    the eight 4x4 chroma blocks, mutation-checked; luma Intra_16x16 cells with them."""
+    req, hit = _i_cells(_i_random_entries(["i_422"]), 8)
+    for k in ("i16", "c", "cdc"):
+        print(f"I census 4:2:2 {k}: required {len(req[k])} hit {len(hit[k])}")
+        assert hit[k] == req[k], (k, sorted(req[k] - hit[k])[:8])
+    assert len(req["cdc"]) == 2 * 8 * 4
+
+
+@pytest.mark.parametrize("name", ["i_top", "i_bottom"])
+def test_census_i_fields(name):
+    """A field picture's sites: all three MB kinds, all four chroma modes, all 16 masks."""
+    c = X.build(name)
+    want = A.TOP_FIELD if name == "i_top" else A.BOTTOM_FIELD
+    assert [int(p.pic["structure"][0]) for p in c.pics] == [want]
+    entries = I.census(name)[0]
+    assert {e["kind"] for e in entries} == {"i4", "i8", "i16", "cb", "cr"}
+    assert {e["mode"] for e in entries if e["kind"] == "cb"} == {0, 1, 2, 3}
+    assert {e["mode"] for e in entries if e["kind"] == "i4"} == set(range(9)) == {e["mode"] for e in entries if e["kind"] == "i8"}
+    assert {s["mask"] for s in c.info["sites"]} == set(I.MASKS)
+
+
+def test_census_i_values():
+    """Every (MB kind, mode) over neighbours that are all 0, all 255, 0 / 255 alternating in both
+    phases and ramps in both directions: the four neighbour MBs hold exactly that pattern."""
+    seen = set()
+    for n in ("i_4x4", "i_8x8", "i_16x16", "i_422"):
+        c = X.build(n)
+        tags = _i_tags(n)
+        ch = A.chroma_mb(c.chroma_format)[1]
+        for e in I.census(n)[0]:
+            s = tags[(e["pic"], e["mb"])]
+            if s["tag"] != "values" or e["blk"] != 0:
+                continue
+            pat = s["pat"]["A"]
+            assert set(s["pat"].values()) == {pat} and s["mask"] == (1, 1, 1, 1)
+            mx, my = e["mb"]
+            for nx, ny in ((mx - 1, my), (mx, my - 1), (mx + 1, my - 1), (mx - 1, my - 1)):
+                for k, (w, h) in enumerate(((16, 16), (8, ch), (8, ch))):
+                    assert np.array_equal(c.refs[e["pic"]][k][h * ny:h * ny + h, w * nx:w * nx + w], I.pattern_mb(pat, w, h, None))
+            seen.add((("c422" if e["kind"] in ("cb", "cr") else e["kind"]) if n == "i_422" else e["kind"], e["mode"], pat))
+    want = {(k, m, pat) for pat in I.PATTERNS for k, nm in (("i4", 9), ("i8", 9), ("i16", 4), ("cb", 4), ("cr", 4), ("c422", 4))
+            for m in range(nm)}
+    assert want <= seen, sorted(want - seen)[:8]
+
+
+def test_census_i_dc_rounding():
+    """For every DC form and each of its two shifts: a neighbour sum whose remainder mod 2^shift is
+    2^(shift - 1) - 1 (the last that rounds down) and one at 2^(shift - 1) (the first that rounds up)."""
+    got = {}
+    for n in I.I_RESTATED:
+        for e in I.census(n)[0]:
+            key = e["kind"] + ("/422" if n == "i_422" and e["kind"] in ("cb", "cr") else "")
+            if "dc" in e:
+                got.setdefault(key, set()).add(e["dc"])
+            for _, sh, rem in e.get("blocks", ()):
+                if rem is not None:
+                    got.setdefault(key, set()).add((sh, rem))
+    for kind, shifts in list(I.DC_SHIFTS.items()) + [("cb/422", (2, 3)), ("cr/422", (2, 3))]:
+        for sh in shifts:
+            assert {(sh, (1 << (sh - 1)) - 1), (sh, 1 << (sh - 1))} <= got[kind], (kind, sh)
+
+
+def test_census_i_plane():
+    """The plane predictors at their extremes, from the logged unclipped values: Intra_16x16 Hs and
+    Vs at +-9180 = 255 (1 + .. + 8); chroma +-2550 = 255 (1 + .. + 4) in 4:2:0 and, vertically, +-9180 in
+    4:2:2 (8.3.4.4 with yCF = 4: eight terms); per kind an MB whose samples clip at 0 AND at 255, and
+    one without any clipping."""
+    for n, kinds in (("i_16x16", (("i16", 9180, 9180), ("cb", 2550, 2550), ("cr", 2550, 2550))),
+                     ("i_422", (("i16", 9180, 9180), ("cb", 2550, 9180), ("cr", 2550, 9180)))):
+        for kind, hmax, vmax in kinds:
+            pl = [e["plane"] for e in I.census(n)[0] if e["kind"] == kind and "plane" in e]
+            assert {hmax, -hmax} <= {h for h, _, _, _ in pl} and {vmax, -vmax} <= {v for _, v, _, _ in pl}, (n, kind)
+            assert max(abs(h) for h, _, _, _ in pl) == hmax and max(abs(v) for _, v, _, _ in pl) == vmax
+            assert any(lo < 0 and hi > 255 for _, _, lo, hi in pl), (n, kind)
+            assert any(lo >= 0 and hi <= 255 for _, _, lo, hi in pl), (n, kind)
+
+
+def test_census_i_edges():
+    """Unavailability by the picture border and by a slice boundary, not by CIP: the border picture is
+    an I picture of intra MBs alone with sites on all four corners and edges; in the slice picture
+    every MB is intra and every neighbour a site misses lies in another slice."""
+    c = X.build("i_edges")
+    W, H = c.pics[0].cfg.width_mbs, c.pics[0].cfg.height_mbs
+    border = {s["mb"]: s["mask"] for s in c.info["sites"] if s["pic"] == 0}
+    assert int(c.pics[0].slices[0]["slice_type"]) == A.SLICE_I and not int(c.pics[0].pic["constrained_intra_pred"][0])
+    assert all(int(m["flags"]) & A.MBF_INTRA for p in c.pics for m in p.mbs)
+    for x, y in ((0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (4, 0), (4, H - 1), (0, 4), (W - 1, 4)):
+        assert border[(x, y)] == (int(x > 0), int(y > 0), int(y > 0 and x < W - 1), int(x > 0 and y > 0))
+    assert set(border.values()) == {(0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 1, 0), (1, 1, 0, 1), (1, 1, 1, 1)}
+    sl = {s["mb"]: s["mask"] for s in c.info["sites"] if s["pic"] == 1}
+    p = c.pics[1]
+    assert len(set(int(s) for s in p.mbs["slice"])) == 4 and int(p.pic["constrained_intra_pred"][0]) == 1
+    assert sl[(7, 3)] == (0, 0, 0, 0) and sl[(9, 3)] == (1, 0, 0, 0) and sl[(4, 3)] == (1, 1, 1, 1)
+    assert sl[(3, 10)] == (1, 0, 0, 0) and sl[(6, 10)] == (1, 0, 1, 0) and sl[(7, 14)] == (1, 1, 1, 0) and sl[(10, 14)] == (1, 1, 1, 1)
+    assert {e["kind"] for e in I.census("i_edges")[0] if e["pic"] == 1} == {"i4", "i8", "i16", "cb", "cr"}
+
+
+def test_census_i_chain():
+    """The chain: in every chain row the dependency levels run 1 .. 7 left to right (so levels above
+    the three list levels exist), the MBs at even levels carry a residual, every list level holds
+    pairable MBs and others, and the residuals are small."""
+    c = X.build("i_chain")
+    assert len(c.pics) == 2
+    for p in c.pics:
+        lv = I.levels_of(p)
+        W = p.cfg.width_mbs
+        for y in range(1, p.cfg.height_mbs, 2):
+            assert list(lv[y, 1:1 + I.CHAIN_LEN]) == list(range(1, I.CHAIN_LEN + 1))
+            coded = [int(p.mbs[y * W + x]["cbp"]) != 0 for x in range(1, 1 + I.CHAIN_LEN)]
+            assert coded == [i % 2 == 1 for i in range(I.CHAIN_LEN)] and sum(coded) * 2 >= I.CHAIN_LEN - 1
+        assert I.CHAIN_LEN >= 6 and lv.max() == I.CHAIN_LEN
+        for level in (1, 2, 3):
+            kinds = [int(p.mbs[a]["mb_type"]) for a in range(len(p.mbs)) if lv.ravel()[a] == level]
+            assert kinds.count(A.I_4x4) >= 2 and (level == 2 or len(kinds) > kinds.count(A.I_4x4))
+        assert int(np.abs(p.levels[[int(m["coef_off"]) for m in p.mbs if int(m["cbp"])]].astype(np.int64)).max()) <= 8
+
+
+def test_census_i_pairs():
+    """The pair list of level 1 (I_4x4, not lossless): over all pictures of a plain case and over all
+    but the last its count has different parities, so one of the two batches leaves a single MB over."""
+    for n in I.I_PLAIN:
+        c = X.build(n)
+        counts = [I.pairable_level1(p) for p in c.pics]
+        print(n, "level-1 pairable MBs per picture", counts)
+        assert len(c.pics) >= 2 and counts[-1] % 2 == 1 and sum(counts) > 2, (n, counts)
+
+
+def test_census_i_mbaff():
+    """The weaker census of the generated MBAFF case (no restatement: it is pinned to the reference
+    alone): every (kind, mode) occurs in a frame MB and in a field MB, every I_4x4 (blkIdx, mode) and
+    I_8x8 (blk, mode) occurs; no intra MB has a residual; the I_PCM MBs hold the value patterns."""
+    c = X.build("i_mbaff")
+    assert c.info == dict(seed=I.MBAFF_SEED, size=(I.MBAFF_W, I.MBAFF_H))
+    kinds, c4, c8 = I.mbaff_census(c)
+    print(f"I census MBAFF: (kind, mode, frame / field) {len(kinds)} of 52, I_4x4 (blkIdx, mode) {len(c4)} of 144, "
+          f"I_8x8 (blk, mode) {len(c8)} of 36")
+    want = {(k, m, f) for k, n in (("i4", 9), ("i8", 9), ("i16", 4), ("c", 4)) for m in range(n) for f in (False, True)}
+    assert kinds == want, sorted(want - kinds)
+    assert c4 == {(b, m) for b in range(16) for m in range(9)} and c8 == {(b, m) for b in range(4) for m in range(9)}
+    flat = set()
+    for p in c.pics:
+        assert int(p.pic["structure"][0]) == A.MBAFF_FRAME and int(p.pic["constrained_intra_pred"][0]) == 1
+        for m in p.mbs:
+            if int(m["mb_type"]) == A.I_PCM:
+                raw = p.levels[int(m["coef_off"]):int(m["coef_off"]) + 128].view(np.uint8)
+                flat |= {int(raw[0])} if (raw == raw[0]).all() else set()
+            elif int(m["flags"]) & A.MBF_INTRA:
+                assert int(m["cbp"]) == 0 and int(m["cbp_blks"]) == 0
+    assert flat == {0, 255}

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 S_PLAIN = [n for n in X.S_CASES if n not in ("s_422_v", "s_mbaff_v")]
 ALL_SCHEDULES = X.D_CASES + ["w_explicit_b_flat"] + S_PLAIN      # the D and S cases and one B case: all four schedules
-SPECIAL = {"x_422_p", "s_422_v"}                         # their own context (chroma_format_idc 2)
+SPECIAL = {"x_422_p", "s_422_v", "i_422"}                # their own context (chroma_format_idc 2)
 
 
 @pytest.fixture(scope="module")
