@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "h264r.h"
+#include "output_job.h"
 #include "picture_stage.h"
 
 #define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -90,6 +91,7 @@ struct h264r_ctx {
     DevBuf<int> d_err;                    // [0] device error word (a bounded wait expired), [1] wait bound
     uint32_t wait_ticks = 0;              // err[1] as last written (s_memrealtime ticks, 100 MHz)
     uint32_t wait_val = 0;                // its host copy, the source of the async write
+    DevBuf<h264r::BoxPlan> d_box_plans;   // h264r_output_rgb_boxes: a plan per box of the largest job so far
     // streaming-API staging: two pictures, so that one is parsed (h264r_picture_begin /
     // h264r_mb_submit) while the other is reconstructed (h264r_picture_end_async)
     struct StreamPic {

@@ -1,5 +1,6 @@
 // host_output.hip -- the output stage of include/h264r_output.h on the host: the geometry and layout
-// of cropped, RGB and scaled RGB frames, and the launches of k_output.hip / k_output_scale.hip.
+// of cropped, RGB and scaled RGB frames and of the images of a boxes job, and the launches of k_output.hip /
+// k_output_scale.hip / k_output_boxes.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include "h264r_output.h"
 #include "host_ctx.h"
 #include "kernels.h"
+#include "output_boxes.h"
 
 // ------------------------------------------------------------- output stage (h264r_output.h)
 // The planes of one output frame: the geometry (output.cc:135-165) and the layout, as the job k_output
@@ -313,6 +315,99 @@ int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h2
     const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
     hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
                        static_cast<uint8_t*>(dst), c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- boxes of scaled RGB (h264r_output.h)
+// The layout of one image and the job the k_output_boxes kernels take: all of it but the tables' sizes.
+// Argument errors come before what is merely unsupported, as in scale_plan; with H264R_EUNSUPPORTED the
+// job holds what bounds a box (the cropped rectangle, the image, max_out, the filter) and nothing else.
+static int boxes_plan(int fmt, const h264r_boxes_desc* d, h264r_rgb_geom* g, h264r::BoxesJob* job)
+{
+    if (!d) return H264R_EINVAL;
+    int32_t full[2];
+    h264r::RgbJob R;
+    const int st = rgb_source(fmt, &d->rgb, full, &R);
+    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
+    if (d->image_w < 1 || d->image_w > H264R_SCALE_MAX_OUT || d->image_h < 1 || d->image_h > H264R_SCALE_MAX_OUT ||
+        d->max_out_w < 1 || d->max_out_w > d->image_w || d->max_out_h < 1 || d->max_out_h > d->image_h ||
+        (d->filter != H264R_SCALE_BILINEAR && d->filter != H264R_SCALE_AREA) || d->pad != 0)
+        return H264R_EINVAL;
+    if (st != H264R_OK) {                                   // the bounds of a box are known all the same
+        if (job) {
+            *job = h264r::BoxesJob{};
+            job->rgb.lw = full[0]; job->rgb.lh = full[1];
+            job->image_w = d->image_w; job->image_h = d->image_h;
+            job->max_out_w = d->max_out_w; job->max_out_h = d->max_out_h;
+            job->filter = d->filter;
+        }
+        return st;
+    }
+    rgb_layout(d->rgb.format, d->rgb.src.pitch_align, d->image_w, d->image_h, g, &R);
+    if (job) {
+        h264r::BoxesJob J{};
+        J.rgb = R;
+        J.image_w = d->image_w; J.image_h = d->image_h;
+        J.max_out_w = d->max_out_w; J.max_out_h = d->max_out_h;
+        J.filter = d->filter;
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+int h264r_output_rgb_boxes_geometry(int chroma_format_idc, const h264r_boxes_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return boxes_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_out_box_status(int chroma_format_idc, const h264r_boxes_desc* desc, const h264r_out_box* box, int num_frames,
+                         int num_images)
+{
+    if (!box || num_frames < 0 || num_images < 0) return H264R_EINVAL;
+    h264r::BoxesJob job;
+    const int st = boxes_plan(chroma_format_idc, desc, nullptr, &job);
+    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
+    job.rgb.num_frames = num_frames;
+    job.num_images = num_images;
+    const int bs = h264r::out_box_status(*box, job);
+    // every argument error before anything unsupported: the descriptor's, then the box's
+    return bs == H264R_EINVAL || st == H264R_OK ? bs : st;
+}
+
+int h264r_output_rgb_boxes(h264r_ctx* c, const h264r_boxes_desc* desc, const h264r_out_frame* frames, int num_frames,
+                           const h264r_out_box* boxes, int num_boxes, void* dst, int64_t dst_image_stride, int num_images,
+                           void* stream)
+{
+    if (!c || !frames || !boxes || !dst || num_frames < 0 || num_boxes < 0 || num_images < 0) return H264R_EINVAL;
+    h264r::BoxesJob job;
+    const int st = boxes_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (!rgb_dst_ok(job.rgb, dst, dst_image_stride)) return H264R_EINVAL;
+    if (num_boxes == 0) return H264R_OK;
+    job.rgb.frame_stride = dst_image_stride;
+    job.rgb.num_frames = num_frames;
+    job.num_boxes = num_boxes;
+    job.num_images = num_images;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    // the plans: the buffer grows only when a job has more boxes than any before it
+    if (const int e = c->d_box_plans.reserve((size_t)num_boxes)) return e;
+    hipLaunchKernelGGL(k_output_boxes_plan, dim3((unsigned)((num_boxes + h264r::BOXES_PLAN_THREADS - 1) / h264r::BOXES_PLAN_THREADS)),
+                       dim3(h264r::BOXES_PLAN_THREADS), 0, s, job, frames, boxes, c->d_box_plans.p, c->d_err.p);
+    HIP_OK(hipGetLastError());
+    // the kernel of the job's mode and filter; box z * grid.y + y, so that one launch holds any number
+    using BoxesKernel = void (*)(h264r::BoxesJob, const h264r_out_frame*, const h264r::BoxPlan*, uint8_t*);
+    BoxesKernel kernel[h264r::RGB_BIL2 + 1][2] = {};
+#define H264R_BOXES_KERNEL_ENTRY(NAME, MODE, FILTER) kernel[MODE][FILTER] = k_output_boxes_##NAME;
+    H264R_SCALE_KERNELS(H264R_BOXES_KERNEL_ENTRY)
+#undef H264R_BOXES_KERNEL_ENTRY
+    const int units = job.max_out_h * h264r::rgb_units_per_row(job.max_out_w);
+    const int gy = std::min(num_boxes, 65535);
+    const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_boxes + gy - 1) / gy));
+    hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
+                       static_cast<const h264r::BoxPlan*>(c->d_box_plans.p), static_cast<uint8_t*>(dst));
     HIP_OK(hipGetLastError());
     return H264R_OK;
 }

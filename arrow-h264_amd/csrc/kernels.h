@@ -74,7 +74,8 @@ enum DevErr : int {
     DEV_ERR_MBAFF_REF = 5,
     // MBAFF: what that launch sequence does not decode, k_mbaff.hip (OR-ed by k_mbaff_inter)
     DEV_ERR_MBAFF_REFUSED = 8,
-    // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled)
+    // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled), a refused box
+    // (OR-ed by k_output_boxes_plan)
     DEV_ERR_OUTPUT = 16,
 };
 
@@ -138,3 +139,11 @@ extern "C" __global__ void k_output_rgb(h264r::RgbJob job, const h264r_out_frame
 #define H264R_SCALE_KERNEL_DECL(NAME, MODE, FILTER) \
     extern "C" __global__ void k_output_rgb_scaled_##NAME(h264r::ScaleJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
 H264R_SCALE_KERNELS(H264R_SCALE_KERNEL_DECL)
+// k_output_boxes.hip: boxes of scaled RGB from a device table.  k_output_boxes_plan resolves every box into
+// a BoxPlan (and refuses what out_box_status refuses, output_boxes.h); one kernel k_output_boxes_<name>
+// per RgbMode and filter then writes the pixels of all of them.
+extern "C" __global__ void k_output_boxes_plan(h264r::BoxesJob job, const h264r_out_frame* frames, const h264r_out_box* boxes,
+                                               h264r::BoxPlan* plans, int* err);
+#define H264R_BOXES_KERNEL_DECL(NAME, MODE, FILTER) \
+    extern "C" __global__ void k_output_boxes_##NAME(h264r::BoxesJob job, const h264r_out_frame* frames, const h264r::BoxPlan* plans, uint8_t* dst);
+H264R_SCALE_KERNELS(H264R_BOXES_KERNEL_DECL)

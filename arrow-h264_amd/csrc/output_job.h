@@ -1,7 +1,8 @@
 // output_job.h -- what h264r_output_frames (h264r_host.hip) hands k_output (k_output.hip): the planes
 // of one output frame, resolved from an h264r_out_desc by the geometry of include/h264r_output.h;
-// what h264r_output_rgb hands k_output_rgb (the same file); and what h264r_output_rgb_scaled hands
-// k_output_rgb_scaled (k_output_scale.hip).
+// what h264r_output_rgb hands k_output_rgb (the same file); what h264r_output_rgb_scaled hands
+// k_output_rgb_scaled (k_output_scale.hip); and what h264r_output_rgb_boxes hands the k_output_boxes
+// kernels (k_output_boxes.hip).
 #pragma once
 
 #include <stdint.h>
@@ -92,5 +93,33 @@ struct ScaleJob {
 constexpr int SCALE_THREADS = 256; // k_output_rgb_scaled: threads per workgroup = output pixels = 16 units of RGB_UNIT
 constexpr int SCALE_UNITS = SCALE_THREADS / RGB_UNIT;
 constexpr int64_t SCALE_AREA_MAX_T = 1 << 23;
+
+// What h264r_output_rgb_boxes hands the k_output_boxes kernels (k_output_boxes.hip): the RgbJob of its
+// h264r_rgb_desc, whose source side is that of the full-size RGB frame and whose output side (plane_off,
+// pitch, frame_stride) is the IMAGE's, and what bounds every box.  What k_output_rgb_scaled takes as
+// kernel arguments -- the axes, the region, taps, T -- is per box here: k_output_boxes_plan writes one
+// BoxPlan per box, and the workgroups of k_output_boxes_<mode>_<filter> read theirs.
+struct BoxesJob {
+    RgbJob rgb;                // rgb.num_frames: entries of the frame table
+    int32_t image_w, image_h;
+    int32_t max_out_w, max_out_h;
+    int32_t filter;            // H264R_SCALE_*
+    int32_t num_boxes, num_images;
+};
+
+struct BoxPlan {
+    ScaleAxis ax, ay;          // columns, rows: as ScaleJob's
+    int32_t roi_x, roi_y;
+    int32_t taps;
+    uint32_t T;
+    float inv_2T;
+    int32_t units, upr;        // units of RGB_UNIT output pixels: out_h * upr in all, 0: a refused box, nothing to do
+    int32_t kind;              // of the frame-table entry, tested
+    int32_t frame, image;
+    int32_t dst_x, dst_y;
+};
+static_assert(sizeof(BoxPlan) == 96, "BoxPlan layout");
+
+constexpr int BOXES_PLAN_THREADS = 256;   // k_output_boxes_plan: threads per workgroup = boxes
 
 }  // namespace h264r

@@ -1,5 +1,5 @@
-// output_rgb.h -- the device code the two RGB kernels share: k_output_rgb (k_output.hip) and
-// the k_output_rgb_scaled kernels (k_output_scale.hip).  The unaligned global loads, the 16-pixel source
+// output_rgb.h -- the device code the RGB kernels share: k_output_rgb (k_output.hip), the
+// k_output_rgb_scaled kernels (k_output_scale.hip) and the k_output_boxes kernels (k_output_boxes.hip).  The unaligned global loads, the 16-pixel source
 // unit and its fetch (rgb_fetch_at), the matrix for one pixel (rgb_pixel), and the unit's way out: the
 // format's bytes, interleaved in registers and stored as widely as the destination allows.  There is one
 // fetch and one conversion; what differs between the kernels is how a row's address and a partial

@@ -307,6 +307,90 @@ def scaled_geometry(desc: ScaleDesc, chroma_format: int = 1) -> RgbGeometry:
     return _rgb_geometry("h264r_output_rgb_scaled_geometry", desc, chroma_format)
 
 
+# --------------------------------------------------------------------------------------------
+# Boxes of scaled RGB from a device table (include/h264r_output.h, h264r_output_rgb_boxes).
+# h264r_out_box: frame, image, roi_x, roi_y, roi_w, roi_h, dst_x, dst_y, out_w, out_h, pad[2]
+OUT_BOX_DTYPE = np.dtype([("frame", "<i4"), ("image", "<i4"), ("roi_x", "<i4"), ("roi_y", "<i4"), ("roi_w", "<i4"),
+                          ("roi_h", "<i4"), ("dst_x", "<i4"), ("dst_y", "<i4"), ("out_w", "<i4"), ("out_h", "<i4"),
+                          ("pad", "<i4", (2,))])
+assert OUT_BOX_DTYPE.itemsize == 48
+
+
+class OutBox(C.Structure):
+    """h264r_out_box"""
+    _fields_ = [("frame", C.c_int32), ("image", C.c_int32), ("roi_x", C.c_int32), ("roi_y", C.c_int32),
+                ("roi_w", C.c_int32), ("roi_h", C.c_int32), ("dst_x", C.c_int32), ("dst_y", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class BoxesDesc(C.Structure):
+    """h264r_boxes_desc"""
+    _fields_ = [("rgb", RgbDesc), ("image_w", C.c_int32), ("image_h", C.c_int32), ("max_out_w", C.c_int32),
+                ("max_out_h", C.c_int32), ("filter", C.c_int32), ("pad", C.c_int32)]
+
+
+def boxes_desc(rgb: RgbDesc, image_w: int, image_h: int, max_out=None, filter: int = SCALE_AREA) -> BoxesDesc:
+    """An h264r_boxes_desc over a copy of `rgb`; max_out = (w, h) bounds every box's output size, None =
+    the image's size."""
+    mw, mh = (image_w, image_h) if max_out is None else max_out
+    return BoxesDesc(RgbDesc.from_buffer_copy(rgb), int(image_w), int(image_h), int(mw), int(mh), int(filter), 0)
+
+
+def boxes_geometry(desc: BoxesDesc, chroma_format: int = 1) -> RgbGeometry:
+    """h264r_output_rgb_boxes_geometry (host only, no GPU): the layout of one image; raises H264RError with
+    the library's status."""
+    return _rgb_geometry("h264r_output_rgb_boxes_geometry", desc, chroma_format)
+
+
+def boxes_table(boxes) -> np.ndarray:
+    """A host box table (OUT_BOX_DTYPE) of `boxes`: such an array already, or an iterable of boxes, each a
+    mapping or a sequence (frame, image, roi_x, roi_y, roi_w, roi_h, dst_x, dst_y, out_w, out_h)."""
+    if isinstance(boxes, np.ndarray) and boxes.dtype == OUT_BOX_DTYPE:
+        return np.ascontiguousarray(boxes.reshape(-1))
+    rows = list(boxes)
+    tab = np.zeros(len(rows), OUT_BOX_DTYPE)
+    names = OUT_BOX_DTYPE.names[:10]
+    for i, row in enumerate(rows):
+        if hasattr(row, "keys"):
+            for k in row.keys():
+                tab[i][k] = row[k]
+        else:
+            if len(row) != 10:
+                raise ValueError("a box is (frame, image, roi_x, roi_y, roi_w, roi_h, dst_x, dst_y, out_w, out_h)")
+            for k, v in zip(names, row):
+                tab[i][k] = int(v)
+    return tab
+
+
+def box_status(desc: BoxesDesc, box, num_frames: int, num_images: int, chroma_format: int = 1) -> int:
+    """h264r_out_box_status (host only, no GPU) of one box -- an OutBox, or one row of a box table: the
+    library's status, H264R_OK for a box the device writes."""
+    from . import lib
+    if not isinstance(box, OutBox):
+        box = OutBox.from_buffer_copy(np.asarray(box, OUT_BOX_DTYPE).reshape(1).tobytes())
+    return int(lib().h264r_out_box_status(chroma_format, C.byref(desc), C.byref(box), num_frames, num_images))
+
+
+def letterbox_boxes(n: int, lw: int, lh: int, image_w: int, image_h: int) -> np.ndarray:
+    """The box table of a letterbox: frame i of n whole (lw x lh its cropped size) into image i, aspect
+    kept, centred in image_w x image_h.  In integers: the axis that fills the image is the one the frame
+    is longer in (lw * image_h <= lh * image_w: the height), the other is the nearest integer to the
+    scaled size, 1 at the least; the border the caller has filled stays."""
+    if min(n + 1, lw, lh, image_w, image_h) < 1:
+        raise ValueError("letterbox_boxes: sizes must be positive")
+    if lw * image_h <= lh * image_w:
+        out_h = image_h
+        out_w = max(1, (2 * lw * image_h + lh) // (2 * lh))
+    else:
+        out_w = image_w
+        out_h = max(1, (2 * lh * image_w + lw) // (2 * lw))
+    tab = np.zeros(n, OUT_BOX_DTYPE)
+    tab["frame"] = tab["image"] = np.arange(n)
+    tab["out_w"], tab["out_h"] = out_w, out_h
+    tab["dst_x"], tab["dst_y"] = (image_w - out_w) // 2, (image_h - out_h) // 2
+    return tab
+
+
 def bind(L) -> None:
     """Declare the prototypes of include/h264r_output.h on the library (h264r.lib())."""
     P, I = C.c_void_p, C.c_int
@@ -324,6 +408,12 @@ def bind(L) -> None:
     L.h264r_output_rgb_scaled_geometry.restype = I
     L.h264r_output_rgb_scaled.argtypes = [P, C.POINTER(ScaleDesc), P, I, P, C.c_int64, P]
     L.h264r_output_rgb_scaled.restype = I
+    L.h264r_output_rgb_boxes_geometry.argtypes = [I, C.POINTER(BoxesDesc), C.POINTER(RgbGeom)]
+    L.h264r_output_rgb_boxes_geometry.restype = I
+    L.h264r_out_box_status.argtypes = [I, C.POINTER(BoxesDesc), C.POINTER(OutBox), I, I]
+    L.h264r_out_box_status.restype = I
+    L.h264r_output_rgb_boxes.argtypes = [P, C.POINTER(BoxesDesc), P, I, P, I, P, C.c_int64, I, P]
+    L.h264r_output_rgb_boxes.restype = I
 
 
 @dataclass(frozen=True)
@@ -487,3 +577,58 @@ class DeviceOutput:
             return d, scaled_geometry(d, self.chroma_format)
         dst, n, g = self._call("rgb_scaled", "h264r_output_rgb_scaled", plan, table, n, dst, stream)
         return rgb_view(dst[:n], g, format)
+
+    def rgb_boxes(self, table, boxes, image_w: int, image_h: int, num_images: int, *, n: int | None = None,
+                  num_boxes: int | None = None, max_out=None, filter: int = SCALE_AREA, matrix: int = CSC_BT709,
+                  full_range: bool = False, chroma_up: int = UP_REPLICATE, format: int = RGB_PLANAR_U8, bgr: bool = False,
+                  alpha: int = 255, scale=(1 / 255,) * 3, bias=(0,) * 3, dst=None, stream: int | None = None):
+        """h264r_output_rgb_boxes: every box of `boxes` -- a region of a frame of the table, resampled by
+        `filter` to the box's own size -- into its place in one of num_images images of image_w x image_h,
+        in one job.  boxes: a host table (boxes_table's input: an OUT_BOX_DTYPE array or an iterable of
+        boxes), uploaded here; or a torch uint8 tensor on the device that holds h264r_out_box records; or
+        a raw device address with num_boxes.  max_out = (w, h) bounds every box's output size (None: the
+        image's size; the launch is sized by it).  The other keywords and the tensor returned are those of
+        rgb(), at the image size: [num_images, image_h, image_w, 3 | 4] or [num_images, 3, image_h,
+        image_w]; this geometry's pitch_align pads the image rows.  dst: a torch uint8 tensor [num_images,
+        dst_image_stride] on the device, of which only the boxes' pixels are written, or None = new
+        ZERO-FILLED images.  Asynchronous on `stream`, as run()."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("rgb_boxes: n is needed with a raw frame table")
+        keep = None
+        if hasattr(boxes, "data_ptr"):
+            if boxes.dtype != torch.uint8 or not boxes.is_contiguous() or boxes.numel() % OUT_BOX_DTYPE.itemsize:
+                raise ValueError("rgb_boxes: a device box table is a contiguous uint8 tensor of 48-byte records")
+            num_boxes = boxes.numel() // OUT_BOX_DTYPE.itemsize if num_boxes is None else num_boxes
+            bptr = boxes.data_ptr()
+        elif isinstance(boxes, int):
+            if num_boxes is None:
+                raise ValueError("rgb_boxes: num_boxes is needed with a raw box table")
+            bptr = boxes
+        else:
+            tab = boxes_table(boxes)
+            num_boxes = len(tab) if num_boxes is None else num_boxes
+            # one record more than the table holds: an empty table still has an address
+            raw = np.concatenate([tab.view(np.uint8).reshape(-1), np.zeros(OUT_BOX_DTYPE.itemsize, np.uint8)])
+            keep = torch.from_numpy(raw).to("cuda")
+            bptr = keep.data_ptr()
+        d = boxes_desc(rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias), image_w, image_h,
+                       max_out, filter)
+        g = boxes_geometry(d, self.chroma_format)
+        if dst is None:
+            dst = torch.zeros((num_images, g.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < num_images or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("rgb_boxes: dst must be a uint8 tensor [num_images, dst_image_stride] with contiguous rows")
+        _check("h264r_output_rgb_boxes",
+               self.decoder._L.h264r_output_rgb_boxes(self.decoder.handle, C.byref(d), C.c_void_p(tptr), n, C.c_void_p(bptr),
+                                                      num_boxes, C.c_void_p(dst.data_ptr()), dst.stride(0), num_images,
+                                                      C.c_void_p(stream or 0)))
+        if keep is not None:
+            self._box_tables = [keep]                       # alive until the next job replaces it
+        return rgb_view(dst[:num_images], g, format)

@@ -306,6 +306,97 @@ int h264r_output_rgb_scaled_geometry(int chroma_format_idc, const h264r_scale_de
 int h264r_output_rgb_scaled(h264r_ctx* ctx, const h264r_scale_desc* desc, const h264r_out_frame* frames /*device*/,
                             int num_frames, void* dst /*device*/, int64_t dst_frame_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Boxes: h264r_output_rgb_boxes takes the region, the output size and the placement from a DEVICE table,
+ * one h264r_out_box per box, and writes every box of the table in one job: a detector's boxes each to a
+ * classifier's input size, a letterbox (the whole frame, aspect kept, centred in a canvas whose border the
+ * caller has filled), several frames into one mosaic.  The meaning is by composition with the two
+ * definitions above; nothing is resampled differently.
+ *
+ * An image.  The job writes into num_images destination images of image_w x image_h pixels, image k at
+ * dst + k * dst_image_stride.  The layout of one image is that of h264r_output_rgb_geometry with
+ * (image_w, image_h) in place of (lw, lh) -- the same four formats, rgb.src.pitch_align pads the IMAGE
+ * rows -- and it is what h264r_output_rgb_boxes_geometry returns (width, height = image_w, image_h).
+ *
+ * A box b names out_h rows of out_w pixels, each three 8-bit values v (one per channel c0, c1, c2):
+ * exactly the values h264r_output_rgb_scaled defines for the same `rgb`, the frame-table entry b.frame,
+ * the region (roi_x, roi_y, roi_w, roi_h) -- w == h == 0 stands for the whole cropped rectangle -- the
+ * output size (out_w, out_h) and `filter`.
+ *
+ * Placement.  Pixel (r, x) of the box, r = 0 .. out_h - 1, x = 0 .. out_w - 1, is pixel
+ * (dst_y + r, dst_x + x) of image b.image, written in the image's format: PACKED_U8, PACKED_U8X4 (alpha as
+ * in h264r_output_rgb) and PLANAR_U8 store v, PLANAR_F16 stores half_rn(float(v) * scale[c] + bias[c]) by
+ * the same three operations, not fused.
+ *
+ * What is written.  Only the bytes of the boxes' pixels.  Every other byte of dst keeps what it held: the
+ * pixels of an image no box covers (a letterbox border is the caller's prefill), the padding a pitch_align
+ * leaves behind a row, the bytes between frame_bytes and dst_image_stride, whole images that no box names.
+ * Where two boxes overlap in one image, each channel of each pixel they share holds the value of one of
+ * them; which one is not defined.  Frames may be named by any number of boxes, in any order, or by none.
+ *
+ * Reads.  As for h264r_output_rgb_scaled: no byte outside a source plane and none outside the crop.
+ *
+ * The refusal of a box: ONE rule, the same function on the host (h264r_out_box_status) and on the device,
+ * every field tested before it indexes anything.  In this order,
+ *   H264R_EINVAL       frame outside 0 .. num_frames - 1, image outside 0 .. num_images - 1;
+ *                      a region h264r_output_rgb_scaled_geometry refuses: a negative roi_x / roi_y / roi_w /
+ *                      roi_h, exactly one of roi_w and roi_h zero, a region that reaches outside the cropped
+ *                      rectangle;
+ *                      out_w outside 1 .. max_out_w, out_h outside 1 .. max_out_h;
+ *                      a placement that reaches outside the image: dst_x or dst_y negative,
+ *                      dst_x + out_w > image_w, dst_y + out_h > image_h;
+ *                      a non-zero pad;
+ *   H264R_EUNSUPPORTED (when nothing above applies) H264R_SCALE_AREA with rw * rh > 2^23, rw and rh as in
+ *                      the scaled definition.
+ * On the device a refused box is skipped -- none of its bytes is written -- the context's error word is
+ * set (h264r_check: H264R_EDEVICE) and the other boxes are written.  A box whose frame-table entry has a
+ * kind outside 0..3 or a NULL plane the kind needs is skipped in the same way.
+ */
+typedef struct h264r_out_box {          /* 48 bytes; the box table is a DEVICE array of these */
+    int32_t frame;                      /* entry of the frame table */
+    int32_t image;                      /* destination image, 0 .. num_images - 1 */
+    int32_t roi_x, roi_y, roi_w, roi_h; /* as h264r_scale_desc: luma samples of the cropped rectangle; w == h == 0: all */
+    int32_t dst_x, dst_y;               /* where the box's pixel (0, 0) goes in the image, in pixels */
+    int32_t out_w, out_h;               /* 1 .. desc.max_out_w / max_out_h */
+    int32_t pad[2];                     /* 0 */
+} h264r_out_box;
+
+typedef struct h264r_boxes_desc {
+    h264r_rgb_desc rgb;                 /* everything of h264r_output_rgb; rgb.src.pitch_align pads the IMAGE rows */
+    int32_t image_w, image_h;           /* 1 .. H264R_SCALE_MAX_OUT */
+    int32_t max_out_w, max_out_h;       /* 1 .. image_w / image_h: bound of every box's out_w / out_h (sizes the grid) */
+    int32_t filter, pad;                /* H264R_SCALE_*, 0 */
+} h264r_boxes_desc;
+
+/* Host only, no GPU needed.  geom->width, height = image_w, image_h; the layout of one image as above.
+ * H264R_EINVAL: whatever h264r_output_rgb_geometry refuses for desc->rgb; image_w or image_h outside
+ * 1..16384; max_out_w outside 1..image_w, max_out_h outside 1..image_h; a filter other than the two; a
+ * non-zero pad; a NULL argument.  H264R_EUNSUPPORTED (when nothing above applies): H264R_CSC_GBR with
+ * chroma_format_idc != 3. */
+int h264r_output_rgb_boxes_geometry(int chroma_format_idc, const h264r_boxes_desc* desc, h264r_rgb_geom* geom);
+
+/* Host only, no GPU needed: the rule above for one box (host memory) of a job of num_frames frame-table
+ * entries and num_images images.  H264R_EINVAL also for a NULL box, negative counts and a descriptor
+ * h264r_output_rgb_boxes_geometry refuses with H264R_EINVAL; every H264R_EINVAL comes before any
+ * H264R_EUNSUPPORTED (the descriptor's, then the box's). */
+int h264r_out_box_status(int chroma_format_idc, const h264r_boxes_desc* desc, const h264r_out_box* box, int num_frames,
+                         int num_images);
+
+/* Write the num_boxes boxes of the device table `boxes` into the num_images images at dst.  Two kernel
+ * launches per job whatever the number of boxes (a plan per box, then the pixels of all of them);
+ * asynchronous on `stream` under the stream rules of the other three entry points; num_boxes == 0 is
+ * H264R_OK and does nothing.  dst may have any alignment (PLANAR_F16: a multiple of 2, and so
+ * dst_image_stride); a run of 16 pixels of a box whose destination is 16-byte aligned is written with
+ * 16-byte stores.  The context keeps the plans in a buffer of its own that grows only when num_boxes
+ * exceeds what it has held before.
+ * H264R_EINVAL / H264R_EUNSUPPORTED as h264r_output_rgb_boxes_geometry for the context's chroma format,
+ * and H264R_EINVAL for NULL ctx / frames / boxes / dst, num_frames < 0, num_boxes < 0, num_images < 0,
+ * dst_image_stride < frame_bytes.  Both tables are read on the device, so their mistakes are found there,
+ * as described above. */
+int h264r_output_rgb_boxes(h264r_ctx* ctx, const h264r_boxes_desc* desc, const h264r_out_frame* frames /*device*/, int num_frames,
+                           const h264r_out_box* boxes /*device*/, int num_boxes,
+                           void* dst /*device*/, int64_t dst_image_stride, int num_images, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
