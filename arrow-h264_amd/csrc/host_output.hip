@@ -1,16 +1,20 @@
 // host_output.hip -- the output stage of include/h264r_output.h on the host: the geometry and layout
-// of cropped, RGB and scaled RGB frames and of the images of a boxes job, and the launches of k_output.hip /
-// k_output_scale.hip / k_output_boxes.hip.
+// of cropped, RGB, scaled and resampled RGB frames and of the images of a boxes job, the plans of the
+// resampler (its tables come from resample_tables.h), and the launches of k_output.hip / k_output_scale.hip /
+// k_output_boxes.hip / k_output_resample.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <new>
+#include <vector>
 
 #include "h264r.h"
 #include "h264r_output.h"
 #include "host_ctx.h"
 #include "kernels.h"
 #include "output_boxes.h"
+#include "resample_tables.h"
 
 // ------------------------------------------------------------- output stage (h264r_output.h)
 // The planes of one output frame: the geometry (output.cc:135-165) and the layout, as the job k_output
@@ -314,6 +318,153 @@ int h264r_output_rgb_scaled(h264r_ctx* c, const h264r_scale_desc* desc, const h2
     const int gy = std::min(num_frames, 65535);
     const dim3 grid((unsigned)((units + h264r::SCALE_UNITS - 1) / h264r::SCALE_UNITS), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
     hipLaunchKernelGGL(kernel[job.rgb.mode][job.filter], grid, dim3(h264r::SCALE_THREADS), 0, s, job, frames,
+                       static_cast<uint8_t*>(dst), c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- resampled RGB frames (h264r_output.h)
+// A plan: the job the k_output_rgb_resampled kernels take, whose table pointers are into `tab`.
+struct h264r_resample_plan {
+    h264r_ctx* ctx = nullptr;         // compared, never dereferenced: a plan may outlive its context
+    int device = 0;
+    h264r::ResampleJob job{};
+    h264r::DevBuf<int32_t> tab;       // xmin, count, kk of the columns, then of the rows
+    int lds_bytes = 0;
+};
+
+// The region and the layout of one resampled frame, and the job's RGB side.  Argument errors come before
+// what is merely unsupported, as in scale_plan.  in[] = in0, in1 of the columns, then of the rows.
+static int resample_plan(int fmt, const h264r_resample_desc* d, h264r_rgb_geom* g, h264r::RgbJob* job, int32_t in[4])
+{
+    if (!d) return H264R_EINVAL;
+    int32_t full[2];
+    h264r::RgbJob R;
+    const int st = rgb_source(fmt, &d->rgb, full, &R);
+    if (st != H264R_OK && st != H264R_EUNSUPPORTED) return st;
+    if (d->roi_x < 0 || d->roi_y < 0 || d->roi_w < 0 || d->roi_h < 0 || (d->roi_w == 0) != (d->roi_h == 0) ||
+        d->out_w < 1 || d->out_w > H264R_SCALE_MAX_OUT || d->out_h < 1 || d->out_h > H264R_SCALE_MAX_OUT ||
+        d->filter < H264R_RESAMPLE_TRIANGLE || d->filter > H264R_RESAMPLE_LANCZOS || d->pad != 0)
+        return H264R_EINVAL;
+    const int64_t sw = d->roi_w ? d->roi_w : full[0], sh = d->roi_h ? d->roi_h : full[1];
+    if (d->roi_x + sw > full[0] || d->roi_y + sh > full[1]) return H264R_EINVAL;
+    if (st != H264R_OK) return st;
+    const int32_t r[4] = {d->roi_x, (int32_t)(d->roi_x + sw), d->roi_y, (int32_t)(d->roi_y + sh)};
+    if (h264r::resample_ksize(d->filter, r[0], r[1], d->out_w) > H264R_RESAMPLE_MAX_TAPS ||
+        h264r::resample_ksize(d->filter, r[2], r[3], d->out_h) > H264R_RESAMPLE_MAX_TAPS)
+        return H264R_EUNSUPPORTED;
+    rgb_layout(d->rgb.format, d->rgb.src.pitch_align, d->out_w, d->out_h, g, &R);
+    if (job) *job = R;
+    if (in) for (int k = 0; k < 4; ++k) in[k] = r[k];
+    return H264R_OK;
+}
+
+int h264r_output_rgb_resampled_geometry(int chroma_format_idc, const h264r_resample_desc* desc, h264r_rgb_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return resample_plan(chroma_format_idc, desc, geom, nullptr, nullptr);
+}
+
+int h264r_resample_axis(int filter, int in_size, int in0, int in1, int out_size, int32_t* xmin, int32_t* count, int32_t* kk,
+                        int32_t* ksize)
+{
+    return h264r::resample_axis(filter, in_size, in0, in1, out_size, xmin, count, kk, ksize);
+}
+
+int h264r_resample_plan_create(h264r_ctx* c, const h264r_resample_desc* desc, h264r_resample_plan** plan)
+{
+    if (!c || !desc || !plan) return H264R_EINVAL;
+    *plan = nullptr;
+    h264r::ResampleJob J{};
+    int32_t in[4];
+    const int st = resample_plan(c->fmt, desc, nullptr, &J.rgb, in);
+    if (st != H264R_OK) return st;
+    // both axes on the host: xmin [D], count [D], kk [D][ksize] each, one after the other
+    const int32_t size[2] = {J.rgb.lw, J.rgb.lh}, D[2] = {desc->out_w, desc->out_h};
+    int32_t ks[2];
+    size_t off[2], words = 0;
+    for (int a = 0; a < 2; ++a) {
+        if (h264r::resample_axis(desc->filter, size[a], in[2 * a], in[2 * a + 1], D[a], nullptr, nullptr, nullptr, &ks[a])) return H264R_EINVAL;
+        off[a] = words;
+        words += (size_t)D[a] * (2 + (size_t)ks[a]);
+    }
+    std::vector<int32_t> host(words);
+    for (int a = 0; a < 2; ++a) {
+        int32_t* const p = host.data() + off[a];
+        if (h264r::resample_axis(desc->filter, size[a], in[2 * a], in[2 * a + 1], D[a], p, p + D[a], p + 2 * (size_t)D[a], &ks[a])) return H264R_EINVAL;
+    }
+    // the tiling: the widest tile's columns (from an even column where SubWidthC is 2, in whole units), the
+    // highest tile's rows, and as many rows a step as the LDS holds
+    const bool even = J.rgb.mode >= h264r::RGB_REP;
+    auto span = [&](int a, int tile, bool units) {
+        const int32_t* const lo = host.data() + off[a];
+        const int32_t* const n = lo + D[a];
+        int most = 0;
+        for (int first = 0; first < D[a]; first += tile) {
+            const int last = std::min(first + tile, D[a]) - 1;
+            const int from = units && even ? lo[first] & ~1 : lo[first];
+            const int len = lo[last] + n[last] - from;
+            most = std::max(most, units ? (len + h264r::RGB_UNIT - 1) / h264r::RGB_UNIT * h264r::RGB_UNIT : len);
+        }
+        return most;
+    };
+    J.strip_cols = span(0, h264r::RS_TW, true);
+    J.span_rows = span(1, h264r::RS_TH, false);
+    J.tiles_x = (D[0] + h264r::RS_TW - 1) / h264r::RS_TW;
+    J.tiles_y = (D[1] + h264r::RS_TH - 1) / h264r::RS_TH;
+    J.step_rows = std::min(16, J.span_rows);
+    while (J.step_rows > 1 && h264r::rs_lds_bytes(ks[0], ks[1], J.strip_cols, J.span_rows, J.step_rows) > h264r::RS_LDS_MAX) J.step_rows /= 2;
+    const int lds = h264r::rs_lds_bytes(ks[0], ks[1], J.strip_cols, J.span_rows, J.step_rows);
+    if (lds > h264r::RS_LDS_MAX || (int64_t)J.tiles_x * J.tiles_y > 0x7fffffff) return H264R_EUNSUPPORTED;   // H264R_RESAMPLE_MAX_TAPS rules it out
+
+    h264r_resample_plan* const p = new (std::nothrow) h264r_resample_plan;
+    if (!p) return H264R_ENOMEM;
+    (void)hipSetDevice(c->device);
+    if (const int e = p->tab.reserve(words)) { delete p; return e; }
+    if (hipMemcpy(p->tab.p, host.data(), words * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { delete p; return H264R_EDEVICE; }
+    h264r::ResampleAxis* const ax[2] = {&J.ax, &J.ay};
+    for (int a = 0; a < 2; ++a) {
+        ax[a]->xmin = p->tab.p + off[a];
+        ax[a]->count = ax[a]->xmin + D[a];
+        ax[a]->kk = ax[a]->count + D[a];
+        ax[a]->D = D[a];
+        ax[a]->ksize = ks[a];
+    }
+    p->ctx = c;
+    p->device = c->device;
+    p->job = J;
+    p->lds_bytes = lds;
+    *plan = p;
+    return H264R_OK;
+}
+
+void h264r_resample_plan_destroy(h264r_resample_plan* plan)
+{
+    if (!plan) return;
+    (void)hipSetDevice(plan->device);
+    delete plan;
+}
+
+int h264r_output_rgb_resampled(h264r_ctx* c, const h264r_resample_plan* plan, const h264r_out_frame* frames, int num_frames,
+                               void* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !plan || plan->ctx != c || !frames || !dst || num_frames < 0) return H264R_EINVAL;
+    if (!rgb_dst_ok(plan->job.rgb, dst, dst_frame_stride)) return H264R_EINVAL;
+    if (num_frames == 0) return H264R_OK;
+    h264r::ResampleJob job = plan->job;
+    job.rgb.frame_stride = dst_frame_stride;
+    job.rgb.num_frames = num_frames;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    // the kernel of the job's mode; frame z * grid.y + y, so that one launch holds any number
+    using ResampleKernel = void (*)(h264r::ResampleJob, const h264r_out_frame*, uint8_t*, int*);
+    ResampleKernel kernel[h264r::RGB_BIL2 + 1] = {};
+#define H264R_RESAMPLE_KERNEL_ENTRY(NAME, MODE) kernel[MODE] = k_output_rgb_resampled_##NAME;
+    H264R_RESAMPLE_KERNELS(H264R_RESAMPLE_KERNEL_ENTRY)
+#undef H264R_RESAMPLE_KERNEL_ENTRY
+    const int gy = std::min(num_frames, 65535);
+    const dim3 grid((unsigned)(job.tiles_x * job.tiles_y), (unsigned)gy, (unsigned)((num_frames + gy - 1) / gy));
+    hipLaunchKernelGGL(kernel[job.rgb.mode], grid, dim3(h264r::RS_THREADS), (size_t)plan->lds_bytes, s, job, frames,
                        static_cast<uint8_t*>(dst), c->d_err.p);
     HIP_OK(hipGetLastError());
     return H264R_OK;

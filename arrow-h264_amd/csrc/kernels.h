@@ -74,7 +74,7 @@ enum DevErr : int {
     DEV_ERR_MBAFF_REF = 5,
     // MBAFF: what that launch sequence does not decode, k_mbaff.hip (OR-ed by k_mbaff_inter)
     DEV_ERR_MBAFF_REFUSED = 8,
-    // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled), a refused box
+    // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled, k_output_rgb_resampled), a refused box
     // (OR-ed by k_output_boxes_plan)
     DEV_ERR_OUTPUT = 16,
 };
@@ -147,3 +147,14 @@ extern "C" __global__ void k_output_boxes_plan(h264r::BoxesJob job, const h264r_
 #define H264R_BOXES_KERNEL_DECL(NAME, MODE, FILTER) \
     extern "C" __global__ void k_output_boxes_##NAME(h264r::BoxesJob job, const h264r_out_frame* frames, const h264r::BoxPlan* plans, uint8_t* dst);
 H264R_SCALE_KERNELS(H264R_BOXES_KERNEL_DECL)
+// k_output_resample.hip: Pillow-exact resampled RGB frames, one kernel k_output_rgb_resampled_<name> per RgbMode
+#define H264R_RESAMPLE_KERNELS(X) \
+    X(mono, h264r::RGB_MONO)      \
+    X(full, h264r::RGB_FULL)      \
+    X(gbr, h264r::RGB_GBR)        \
+    X(rep, h264r::RGB_REP)        \
+    X(bil1, h264r::RGB_BIL1)      \
+    X(bil2, h264r::RGB_BIL2)
+#define H264R_RESAMPLE_KERNEL_DECL(NAME, MODE) \
+    extern "C" __global__ void k_output_rgb_resampled_##NAME(h264r::ResampleJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
+H264R_RESAMPLE_KERNELS(H264R_RESAMPLE_KERNEL_DECL)

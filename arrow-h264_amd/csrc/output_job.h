@@ -1,8 +1,9 @@
 // output_job.h -- what h264r_output_frames (h264r_host.hip) hands k_output (k_output.hip): the planes
 // of one output frame, resolved from an h264r_out_desc by the geometry of include/h264r_output.h;
 // what h264r_output_rgb hands k_output_rgb (the same file); what h264r_output_rgb_scaled hands
-// k_output_rgb_scaled (k_output_scale.hip); and what h264r_output_rgb_boxes hands the k_output_boxes
-// kernels (k_output_boxes.hip).
+// k_output_rgb_scaled (k_output_scale.hip); what h264r_output_rgb_boxes hands the k_output_boxes
+// kernels (k_output_boxes.hip); and what h264r_output_rgb_resampled hands the k_output_rgb_resampled
+// kernels (k_output_resample.hip).
 #pragma once
 
 #include <stdint.h>
@@ -121,5 +122,50 @@ struct BoxPlan {
 static_assert(sizeof(BoxPlan) == 96, "BoxPlan layout");
 
 constexpr int BOXES_PLAN_THREADS = 256;   // k_output_boxes_plan: threads per workgroup = boxes
+
+// What h264r_output_rgb_resampled hands the k_output_rgb_resampled kernels (k_output_resample.hip): the
+// RgbJob of its h264r_rgb_desc (source side the full-size RGB frame's, output side the RESAMPLED frame's),
+// the two axis tables of a plan in device memory, and how a workgroup's LDS is cut up for this job.
+constexpr int RS_THREADS = 256;           // threads per workgroup
+constexpr int RS_TW = 16, RS_TH = 16;     // output pixels a workgroup owns: H264R_RESAMPLE_TILE_W / _H
+constexpr int RS_MAX_TAPS = 97;           // H264R_RESAMPLE_MAX_TAPS
+constexpr int RS_LDS_MAX = 65536;         // bytes of LDS a workgroup takes at most
+constexpr int RS_OUT_WORDS = 20;          // words of the job's output side that wait in LDS for the threads that write
+static_assert(RS_TW == RGB_UNIT, "a tile row leaves as one unit of rgb_write");
+
+struct ResampleAxis {
+    const int32_t* xmin;       // [D]
+    const int32_t* count;      // [D]
+    const int32_t* kk;         // [D][ksize]
+    int32_t D, ksize;
+};
+
+struct ResampleJob {
+    RgbJob rgb;
+    ResampleAxis ax, ay;       // columns, rows; xmin counts from the CROPPED rectangle's origin
+    int32_t tiles_x, tiles_y;
+    int32_t strip_cols;        // source columns of the widest tile, from an even column, in whole units: a multiple of 16
+    int32_t span_rows;         // source rows of the highest tile
+    int32_t step_rows;         // source rows converted and passed horizontally at a time
+    int32_t pad;
+};
+
+// LDS of one workgroup, in bytes: kkx [RS_TW][ksx] and kky [RS_TH][ksy] words, xmin and count of the tile's
+// columns and rows, t [span_rows][3][RS_TW] bytes, the strip [step_rows][strip_cols] words (one pixel a
+// word), the tile's 8-bit results [3][RS_TH][RS_TW], and RS_OUT_WORDS words of the job's output side.
+inline __host__ __device__ int rs_t_bytes(int span_rows) { return (span_rows * 3 * RS_TW + 15) & ~15; }
+inline __host__ __device__ int rs_lds_bytes(int ksx, int ksy, int strip_cols, int span_rows, int step_rows)
+{
+    return 4 * (RS_TW * ksx + RS_TH * ksy) + 4 * 2 * (RS_TW + RS_TH) + rs_t_bytes(span_rows) + 4 * step_rows * strip_cols +
+           3 * RS_TH * RS_TW + 4 * RS_OUT_WORDS;
+}
+// The widest job H264R_RESAMPLE_MAX_TAPS admits: ceil(support) <= 48, so support <= 48 and scale <= 48
+// (TRIANGLE).  A tile's windows span (T - 1) * scale + 2 * support + 1 samples at most (xmin is at least
+// center - support + 0.5 - 1, xmax at most center + support + 0.5): 15 * 48 + 97 = 817; the strip starts
+// on an even column (+ 1) and ends on a whole unit (+ 15): 848 columns.
+constexpr int RS_SPAN_MAX = (RS_TH - 1) * 48 + 97;
+constexpr int RS_STRIP_MAX = ((RS_TW - 1) * 48 + 97 + 1 + 15) / 16 * 16;
+static_assert(4 * (RS_TW + RS_TH) * RS_MAX_TAPS + 4 * 2 * (RS_TW + RS_TH) + ((RS_SPAN_MAX * 3 * RS_TW + 15) & ~15) + 4 * RS_STRIP_MAX +
+              3 * RS_TH * RS_TW + 4 * RS_OUT_WORDS <= RS_LDS_MAX, "the widest job fits with one row a step");
 
 }  // namespace h264r

@@ -308,6 +308,76 @@ def scaled_geometry(desc: ScaleDesc, chroma_format: int = 1) -> RgbGeometry:
 
 
 # --------------------------------------------------------------------------------------------
+# Resampled RGB frames (include/h264r_output.h, h264r_output_rgb_resampled): Pillow's 8-bit resize, exactly.
+RESAMPLE_TRIANGLE, RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = 0, 1, 2   # h264r_resample_desc.filter: Pillow BILINEAR, BICUBIC, LANCZOS
+RESAMPLE_MAX_TAPS = 97                                            # H264R_RESAMPLE_MAX_TAPS
+RESAMPLE_TILE_W, RESAMPLE_TILE_H = 16, 16                         # H264R_RESAMPLE_TILE_W / _H: the kernel's tile of output pixels
+
+
+class ResampleDesc(C.Structure):
+    """h264r_resample_desc"""
+    _fields_ = [("rgb", RgbDesc), ("roi_x", C.c_int32), ("roi_y", C.c_int32), ("roi_w", C.c_int32), ("roi_h", C.c_int32),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("filter", C.c_int32), ("pad", C.c_int32)]
+
+
+def resample_desc(rgb: RgbDesc, out_w: int, out_h: int, roi=None, filter: int = RESAMPLE_BICUBIC) -> ResampleDesc:
+    """An h264r_resample_desc over a copy of `rgb`; roi = (x, y, w, h) in luma samples of the cropped
+    rectangle (Pillow's box=(x, y, x + w, y + h)), None = all of it."""
+    x, y, w, h = (0, 0, 0, 0) if roi is None else roi
+    return ResampleDesc(RgbDesc.from_buffer_copy(rgb), int(x), int(y), int(w), int(h), int(out_w), int(out_h), int(filter), 0)
+
+
+def resampled_geometry(desc: ResampleDesc, chroma_format: int = 1) -> RgbGeometry:
+    """h264r_output_rgb_resampled_geometry (host only, no GPU): raises H264RError with the library's status."""
+    return _rgb_geometry("h264r_output_rgb_resampled_geometry", desc, chroma_format)
+
+
+def resample_axis(filter: int, in_size: int, in0: int, in1: int, out_size: int):
+    """h264r_resample_axis (host only, no GPU): the table of one axis as numpy int32 arrays
+    (xmin [out_size], count [out_size], kk [out_size, ksize]); raises H264RError with the library's status."""
+    from . import _check, lib
+    L = lib()
+    ks = C.c_int32(0)
+    _check("h264r_resample_axis", L.h264r_resample_axis(filter, in_size, in0, in1, out_size, None, None, None, C.byref(ks)))
+    xmin, count = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32)
+    kk = np.zeros((out_size, ks.value), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _check("h264r_resample_axis", L.h264r_resample_axis(filter, in_size, in0, in1, out_size, ptr(xmin), ptr(count), ptr(kk),
+                                                        C.byref(ks)))
+    return xmin, count, kk
+
+
+class ResamplePlan:
+    """An h264r_resample_plan of one Decoder: destroyed by close(), at the end of a with block, or when
+    the object goes -- after the launches that use it are done (Decoder.check())."""
+
+    def __init__(self, decoder, desc: ResampleDesc, geom: RgbGeometry):
+        from . import _check
+        self.decoder, self.desc, self.geom = decoder, desc, geom
+        self.format = int(desc.rgb.format)
+        h = C.c_void_p()
+        _check("h264r_resample_plan_create", decoder._L.h264r_resample_plan_create(decoder.handle, C.byref(desc), C.byref(h)))
+        self.handle = h
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.decoder._L.h264r_resample_plan_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self) -> "ResamplePlan":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# --------------------------------------------------------------------------------------------
 # Boxes of scaled RGB from a device table (include/h264r_output.h, h264r_output_rgb_boxes).
 # h264r_out_box: frame, image, roi_x, roi_y, roi_w, roi_h, dst_x, dst_y, out_w, out_h, pad[2]
 OUT_BOX_DTYPE = np.dtype([("frame", "<i4"), ("image", "<i4"), ("roi_x", "<i4"), ("roi_y", "<i4"), ("roi_w", "<i4"),
@@ -414,6 +484,17 @@ def bind(L) -> None:
     L.h264r_out_box_status.restype = I
     L.h264r_output_rgb_boxes.argtypes = [P, C.POINTER(BoxesDesc), P, I, P, I, P, C.c_int64, I, P]
     L.h264r_output_rgb_boxes.restype = I
+    PI32 = C.POINTER(C.c_int32)
+    L.h264r_output_rgb_resampled_geometry.argtypes = [I, C.POINTER(ResampleDesc), C.POINTER(RgbGeom)]
+    L.h264r_output_rgb_resampled_geometry.restype = I
+    L.h264r_resample_axis.argtypes = [I, I, I, I, I, PI32, PI32, PI32, PI32]
+    L.h264r_resample_axis.restype = I
+    L.h264r_resample_plan_create.argtypes = [P, C.POINTER(ResampleDesc), C.POINTER(P)]
+    L.h264r_resample_plan_create.restype = I
+    L.h264r_resample_plan_destroy.argtypes = [P]
+    L.h264r_resample_plan_destroy.restype = None
+    L.h264r_output_rgb_resampled.argtypes = [P, P, P, I, P, C.c_int64, P]
+    L.h264r_output_rgb_resampled.restype = I
 
 
 @dataclass(frozen=True)
@@ -577,6 +658,44 @@ class DeviceOutput:
             return d, scaled_geometry(d, self.chroma_format)
         dst, n, g = self._call("rgb_scaled", "h264r_output_rgb_scaled", plan, table, n, dst, stream)
         return rgb_view(dst[:n], g, format)
+
+    def resample_plan(self, out_w: int, out_h: int, roi=None, filter: int = RESAMPLE_BICUBIC, *, matrix: int = CSC_BT709,
+                      full_range: bool = False, chroma_up: int = UP_REPLICATE, format: int = RGB_PLANAR_U8, bgr: bool = False,
+                      alpha: int = 255, scale=(1 / 255,) * 3, bias=(0,) * 3) -> ResamplePlan:
+        """h264r_resample_plan_create for this geometry: the region `roi` = (x, y, w, h) of every RGB frame
+        (Pillow's box; None = all of it) to out_w x out_h by `filter` (RESAMPLE_*), the other keywords those
+        of rgb().  Synchronous: the tables are built on the host and uploaded.  One plan serves any number
+        of rgb_resampled() calls; close() it (or leave a with block) after they are done."""
+        d = resample_desc(rgb_desc(self.desc, matrix, full_range, chroma_up, format, bgr, alpha, scale, bias), out_w, out_h, roi,
+                          filter)
+        return ResamplePlan(self.decoder, d, resampled_geometry(d, self.chroma_format))
+
+    def rgb_resampled(self, table, plan: ResamplePlan, n: int | None = None, dst=None, stream: int | None = None):
+        """h264r_output_rgb_resampled on the same frame table: n frames (default: the whole table) resampled
+        by `plan` exactly as Pillow's Image.resize would resample the RGB frames, without the full-size
+        frames.  dst and the tensor returned are those of rgb_scaled(): [n, out_h, out_w, 3 | 4] or
+        [n, 3, out_h, out_w]; this geometry's pitch_align pads the output rows.  Asynchronous on `stream`,
+        as run()."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("rgb_resampled: n is needed with a raw frame table")
+        if not plan.handle:
+            raise ValueError("rgb_resampled: the plan is closed")
+        g = plan.geom
+        if dst is None:
+            dst = torch.empty((n, g.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < n or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("rgb_resampled: dst must be a uint8 tensor [n, dst_frame_stride] with contiguous rows")
+        _check("h264r_output_rgb_resampled",
+               self.decoder._L.h264r_output_rgb_resampled(self.decoder.handle, plan.handle, C.c_void_p(tptr), n,
+                                                          C.c_void_p(dst.data_ptr()), dst.stride(0), C.c_void_p(stream or 0)))
+        return rgb_view(dst[:n], g, plan.format)
 
     def rgb_boxes(self, table, boxes, image_w: int, image_h: int, num_images: int, *, n: int | None = None,
                   num_boxes: int | None = None, max_out=None, filter: int = SCALE_AREA, matrix: int = CSC_BT709,

@@ -397,6 +397,124 @@ int h264r_output_rgb_boxes(h264r_ctx* ctx, const h264r_boxes_desc* desc, const h
                            const h264r_out_box* boxes /*device*/, int num_boxes,
                            void* dst /*device*/, int64_t dst_image_stride, int num_images, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Resampled RGB frames: h264r_output_rgb_resampled writes a region of the RGB frame resampled to
+ * out_w x out_h by the 8-bit resampler of Pillow (Image.resize with BILINEAR, BICUBIC or LANCZOS, which
+ * is what most vision models were trained behind), byte for byte, without the full-size frame ever
+ * existing.  The definition is Pillow's Resample.c restated; it is complete here.
+ *
+ * The source.  The three 8-bit channel planes c0, c1, c2 (lh x lw) that h264r_output_rgb defines for the
+ * same h264r_rgb_desc `rgb` and frame-table entry, as for h264r_output_rgb_scaled: the same four kinds,
+ * crop and weave, the 128 rows of an unpaired field, 4:0:0 chroma, chroma_up (its taps clamp to the CROP),
+ * matrix, range, bgr, H264R_CSC_GBR on 4:4:4.  The resampling sees nothing but those planes.
+ *
+ * The region.  roi_x, roi_y, roi_w, roi_h as in h264r_scale_desc (w == h == 0: the whole cropped
+ * rectangle), with the meaning of Pillow's box=:
+ *     resize((out_w, out_h), filter, box=(roi_x, roi_y, roi_x + roi_w, roi_y + roi_h))
+ * applied to the cropped frame.  The region sets where the sample centres fall; a window that reaches past
+ * the region reads the REAL samples of the cropped rectangle there, and clamps only at the crop's edges.
+ * This is not crop(box).resize(...), whose windows clamp at the region's edges.
+ *
+ * The filters f, each with its support; x is binary64 and every operation is written out:
+ *   H264R_RESAMPLE_TRIANGLE (Pillow BILINEAR), support 1:
+ *       x = |x|;  f = 1.0 - x for x < 1.0, else 0.0.
+ *   H264R_RESAMPLE_BICUBIC, support 2, a = -0.5 (torch and OpenCV take a = -0.75: their output is not this):
+ *       x = |x|;  f = ((a + 2.0) * x - (a + 3.0)) * x * x + 1 for x < 1.0,
+ *                 f = (((x - 5) * x + 8) * x - 4) * a for x < 2.0, else 0.0.
+ *   H264R_RESAMPLE_LANCZOS, support 3:
+ *       f = sinc(x) * sinc(x / 3) for -3.0 <= x < 3.0, else 0.0;
+ *       sinc(0.0) = 1.0, else with y = x * 3.14159265358979323846: sinc = sin(y) / y, the C library's sin.
+ *
+ * Per axis, with inSize the crop's size along the axis (lw or lh), in0 the region's origin, in1 = in0 +
+ * the region's size, and outSize; every operation binary64, in this order, none fused:
+ *     scale = (in1 - in0) / outSize        filterscale = max(scale, 1.0)
+ *     support = filter_support * filterscale        ss = 1.0 / filterscale
+ *     ksize = 2 * ceil(support) + 1
+ * and for the output index d:
+ *     center = in0 + (d + 0.5) * scale
+ *     xmin = max(0, (int)(center - support + 0.5))        xmax = min(inSize, (int)(center + support + 0.5))
+ *     k[j] = f((j + xmin - center + 0.5) * ss)   for j = 0 .. xmax - xmin - 1
+ *     ww = sum of k[j] in index order;   k[j] = k[j] / ww when ww != 0
+ *     kk[j] = (int)(k[j] * 2^22 + 0.5) for k[j] >= 0, (int)(k[j] * 2^22 - 0.5) otherwise
+ * where (int) truncates toward zero.  count = xmax - xmin lies in 1 .. ksize.  h264r_resample_axis returns
+ * exactly this table.
+ *
+ * The passes.  With (xminx, kkx) of the columns and (yminy, kky) of the rows, per channel c, >> the
+ * arithmetic shift and clip8(v) = min(max(v, 0), 255):
+ *     t[r][d] = clip8((2^21 + sum over j of kkx[d][j] * c[r][xminx[d] + j]) >> 22)      horizontal, first
+ *     v[e][d] = clip8((2^21 + sum over j of kky[e][j] * t[yminy[e] + j][d]) >> 22)      vertical, over t
+ * The clip between the passes is part of the definition: the negative lobes of BICUBIC and LANCZOS
+ * overshoot, and that is where the overshoot is cut.  At scale 1 on an axis its pass is the identity.
+ * Every accumulator fits 32 bits: 255 * (sum over j of |kk[j]|) + 2^21 < 2^31 for every table (the
+ * normalised taps sum to 2^22; the sum of their magnitudes is largest under LANCZOS, about 1.55 * 2^22 when
+ * upscaling, where 2.005 * 2^22 would be needed to overflow), and every tap lies inside 24 bits.
+ *
+ * The result.  The four formats of h264r_output_rgb apply to v, with bgr, alpha and rgb.src.pitch_align
+ * (which pads the OUTPUT rows) exactly as for h264r_output_rgb_scaled: PLANAR_F16 stores
+ * half_rn(float(v) * scale[c] + bias[c]), the same three operations, not fused.  The layout is that of
+ * h264r_output_rgb_geometry with (out_w, out_h) in place of (lw, lh).
+ *
+ * Bounds.  out_w and out_h lie in 1 .. 16384.  A job whose ksize on either axis exceeds
+ * H264R_RESAMPLE_MAX_TAPS is refused with H264R_EUNSUPPORTED: the constant is what the kernel's LDS holds,
+ * and it admits every job whose scale is at most 16 on both axes under all three filters (LANCZOS at scale
+ * 16: 2 * 48 + 1), TRIANGLE up to scale 48 and BICUBIC up to scale 24.
+ */
+#define H264R_RESAMPLE_TRIANGLE 0   /* Pillow BILINEAR (antialiased) */
+#define H264R_RESAMPLE_BICUBIC  1   /* Pillow BICUBIC */
+#define H264R_RESAMPLE_LANCZOS  2   /* Pillow LANCZOS */
+
+#define H264R_RESAMPLE_MAX_TAPS 97  /* ksize of either axis */
+#define H264R_RESAMPLE_TILE_W   16  /* output pixels a workgroup of the kernel owns: for tests around its edges */
+#define H264R_RESAMPLE_TILE_H   16
+
+typedef struct h264r_resample_desc {
+    h264r_rgb_desc rgb;                 /* everything of h264r_output_rgb; rgb.src.pitch_align pads the OUTPUT rows */
+    int32_t roi_x, roi_y, roi_w, roi_h; /* luma samples inside the cropped rectangle; w == h == 0: all of it */
+    int32_t out_w, out_h;               /* 1..16384 */
+    int32_t filter;                     /* H264R_RESAMPLE_* */
+    int32_t pad;                        /* 0 */
+} h264r_resample_desc;
+
+/* Host only, no GPU needed.  geom->width, height = out_w, out_h; the layout as above.
+ * H264R_EINVAL: what h264r_output_rgb_scaled_geometry refuses with it, with the three filters above in
+ * place of its two.  H264R_EUNSUPPORTED (when nothing above applies): H264R_CSC_GBR with chroma_format_idc
+ * != 3; ksize of either axis above H264R_RESAMPLE_MAX_TAPS. */
+int h264r_output_rgb_resampled_geometry(int chroma_format_idc, const h264r_resample_desc* desc, h264r_rgb_geom* geom);
+
+/* Host only, no GPU needed: the table of one axis, as defined above -- the function a plan builds its
+ * own tables with.  xmin and count hold out_size entries, kk out_size * *ksize (row d: the taps of output
+ * d, zero from count[d] on).  With xmin, count and kk all NULL only *ksize is written; the caller sizes
+ * its arrays by it.  No bound on ksize applies here.
+ * H264R_EINVAL: a filter other than the three, in_size < 1, in0 < 0, in1 <= in0, in1 > in_size, out_size
+ * outside 1..16384, a NULL ksize, some but not all of the three arrays NULL. */
+int h264r_resample_axis(int filter, int in_size, int in0, int in1, int out_size, int32_t* xmin, int32_t* count,
+                        int32_t* kk, int32_t* ksize);
+
+/* A plan: the two tables of one descriptor in device memory the plan owns (tens of kilobytes: more than
+ * kernel arguments carry), with the RGB mode, the layout and the tiling resolved.  Creation is synchronous:
+ * it builds both axes on the host and uploads them with blocking copies.  A plan belongs to the context it
+ * was made on -- its device and its chroma format -- and serves any number of jobs, on any streams, at
+ * once.  The caller destroys it only after the launches that use it are done (h264r_check, or a
+ * synchronisation of their streams); destroying NULL does nothing.
+ * H264R_EINVAL / H264R_EUNSUPPORTED as h264r_output_rgb_resampled_geometry for the context's chroma
+ * format, H264R_EINVAL for a NULL ctx / desc / plan, H264R_ENOMEM. */
+typedef struct h264r_resample_plan h264r_resample_plan;
+int h264r_resample_plan_create(h264r_ctx* ctx, const h264r_resample_desc* desc, h264r_resample_plan** plan);
+void h264r_resample_plan_destroy(h264r_resample_plan* plan);
+
+/* h264r_output_rgb_scaled, resampled by a plan: the same frame table and the same four kinds, ONE launch
+ * per job, asynchronous on `stream` under the same stream rules, num_frames == 0 is H264R_OK.  Frame i
+ * goes to dst + i * dst_frame_stride.  No host arithmetic beyond the argument checks, no allocation, no
+ * copy.  Both passes run inside a workgroup's LDS: no converted and no half-resampled frame exists in
+ * device memory.  Only the bytes of the frames are written; no byte outside a source plane is read, and
+ * none outside the crop.  dst may have any alignment (PLANAR_F16: a multiple of 2, and so dst_frame_stride).
+ * H264R_EINVAL for NULL ctx / plan / frames / dst, a plan of another context, num_frames < 0,
+ * dst_frame_stride < frame_bytes.  A bad kind or a NULL plane is refused on the device as for
+ * h264r_output_rgb: that frame is skipped, the error word is set (h264r_check: H264R_EDEVICE) and the other
+ * frames are written. */
+int h264r_output_rgb_resampled(h264r_ctx* ctx, const h264r_resample_plan* plan, const h264r_out_frame* frames /*device*/,
+                               int num_frames, void* dst /*device*/, int64_t dst_frame_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
