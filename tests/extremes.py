@@ -30,6 +30,14 @@ Families (case names in CASES):
      at +-9180 / +-2550 and clipping at both ends; picture borders, slice boundaries, a chain of
      dependency levels 1..7, field pictures, and a generated MBAFF case with its levels zeroed; checked
      against a restatement of 8.3 in Python integers with a mutation check per cell
+  D2 deblocking thresholds under the settings D leaves out (tests/extremes_d2.py): Cb and Cr under
+     different chroma QP offsets (every record legal: _set_qp(m, qp, offs)), 4:2:2, 4:4:4 and field
+     pictures, by build_d and build_d_every with a pair of offsets per picture and each chroma plane on
+     the thresholds of its own QPc, checked by restating the whole loop filter (deblock_restate with a
+     QP grid per plane and the format's chroma geometry).  MBAFF frames (d_mbaff): crafted MBs in frame
+     and field pairs of every neighbourhood, every class of edge between them on its thresholds,
+     checked against deblock_restate_mbaff.  A mutation check per mistake a kernel could make.
+     r4_chroma_cqp: R4 with Cb and Cr dequantised at different QPs
 tests/test_extremes.py holds the census (each family hits its target, from the inputs and the oracle
 alone) and pins the oracle to the reference decoder on these inputs (tests/golden/extremes.json);
 tests/test_gpu_extremes.py compares the GPU with the oracle.
@@ -488,17 +496,26 @@ def _chroma_units(quant, qp, pl):
     return u
 
 
-def build_r_chroma(L, over_bound: bool) -> Case:
+R4_SPECS = ((0, (0, 0)), (7, (0, 0)))               # (qp_y, chroma QP offsets) per picture
+# Cb and Cr at different qp_scaled, both at QPs whose flat scales reach 32700: (QPc 0, QPc 7) and (7, 0)
+R4_SPECS_CQP = ((3, (-3, 4)), (5, (2, -5)))
+
+
+def build_r_chroma(L, over_bound: bool, specs=R4_SPECS, name=None) -> Case:
     """R4: the chroma measure of inter4_chroma_residual at 32700 (over_bound: one MB per wave at 32701
     or, DC only, the next reachable value): cbpc 2 with the mass in one plane, in the other, and
-    split over the planes in different quadrants; cbpc 1 through the Hadamard."""
+    split over the planes in different quadrants; cbpc 1 through the Hadamard.  With chroma QP offsets
+    (r4_chroma_cqp) every MB's planes are dequantised at different QPs, each plane's levels solved in
+    its own units, and no MB is split: one plane is at the bound, the other far below it."""
     quant = O.quant_flat()[0]
     pics, design = [], []
-    for qp in (0, 7):
-        u = _chroma_units(quant, qp, 0)
+    for qp, co in specs:
+        qpc = [qpc_of(qp, co[pl]) for pl in range(2)]
+        units = [_chroma_units(quant, qpc[pl], pl) for pl in range(2)]
 
-        def ac_block(total, positions, sign=1):
+        def ac_block(total, positions, sign=1, u=None):
             """levels of one plane's 4x4 block (DC excluded) with sum |d| == total on `positions`"""
+            u = units[0] if u is None else u
             n = solve_sum(total, [u[i] for i in positions]) if total else [0] * len(positions)
             assert n is not None, (total, positions)
             lev = [0] * 16
@@ -513,6 +530,7 @@ def build_r_chroma(L, over_bound: bool) -> Case:
             _, cac, _, cdc, _ = layout(m)
             o = int(m["coef_off"])
             cbpc = int(m["cbp"]) >> 4
+            u, uo = units[big_pl], units[1 - big_pl]
             p_.levels[o + cdc:o + cdc + 8] = 0
             if cbpc == 1:
                 assert total % u[0] == 0
@@ -531,35 +549,47 @@ def build_r_chroma(L, over_bound: bool) -> Case:
             p_.levels[o + cdc + big_pl * 4] = dcv
             for cb in range(4):
                 base = o + cac + big_pl * 64 + cb * 16
-                p_.levels[base:base + 16] = ac_block(rest, (1, 4, 5), -1 if cb & 1 else 1)
+                p_.levels[base:base + 16] = ac_block(rest, (1, 4, 5), -1 if cb & 1 else 1, u)
                 other = o + cac + (1 - big_pl) * 64 + cb * 16
-                p_.levels[other:other + 16] = ac_block(total - first, (10, 11, 14, 15)) if split else ac_block(u[1], (1,))
+                p_.levels[other:other + 16] = ac_block(total - first, (10, 11, 14, 15), u=uo) if split else ac_block(uo[1], (1,), u=uo)
 
         p_ = synth.picture(L, _r_cfg(L, qp), 2)
+        cqp = co != (0, 0)
+        if cqp:
+            for m in p_.mbs:
+                _set_qp(m, int(m["qp_y"]), co)
         mbs = [i for i, m in enumerate(p_.mbs) if not int(m["flags"]) & A.MBF_INTRA and int(m["cbp"]) >> 4]
-        at_dc = PK_RES_MAX - PK_RES_MAX % u[0]
+        at_dc = [PK_RES_MAX - PK_RES_MAX % units[pl][0] for pl in range(2)]
         for n, mi in enumerate(mbs):
             m = p_.mbs[mi]
             if int(m["cbp"]) >> 4 == 1:
-                mb_levels(m, n % 2, at_dc)
+                mb_levels(m, n % 2, at_dc[n % 2])
             else:
-                mb_levels(m, n % 2, PK_RES_MAX, split=n % 3 == 2)
+                mb_levels(m, n % 2, PK_RES_MAX, split=n % 3 == 2 and not cqp)
         if over_bound:
             for w in range(0, len(p_.mbs), 4):
                 mine = [mi for mi in mbs if w <= mi < w + 4]
                 if not mine:
                     continue
                 m = p_.mbs[mine[-1]]
+                big = (w // 4) % 2
                 if int(m["cbp"]) >> 4 == 1:
-                    mb_levels(m, (w // 4) % 2, at_dc + u[0])
+                    mb_levels(m, big, at_dc[big] + units[big][0])
                 else:
-                    mb_levels(m, (w // 4) % 2, PK_RES_MAX + (1 if qp < 6 else 2), split=(w // 4) % 2 == 1)   # QP >= 6: even scales
-                design.append((len(pics), w // 4, int(m["cbp"]) >> 4))
+                    mb_levels(m, big, PK_RES_MAX + (1 if qpc[big] < 6 else 2), split=big == 1 and not cqp)   # QP >= 6: even scales
+                design.append((len(pics), w // 4, int(m["cbp"]) >> 4) + ((big,) if cqp else ()))
         recompute_blks(p_)
         check_bounds(p_)
         pics.append(p_)
-    return Case("r4_chroma_over" if over_bound else "r4_chroma_at_bound", pics, synth.refpics(L, pics[0].cfg),
+    return Case(name or ("r4_chroma_over" if over_bound else "r4_chroma_at_bound"), pics, synth.refpics(L, pics[0].cfg),
                 info=dict(design=design))
+
+
+def build_r_chroma_cqp(L) -> Case:
+    """r4_chroma_cqp: the at-bound pictures, then the over-bound ones, under R4_SPECS_CQP."""
+    at, over = (build_r_chroma(L, ob, R4_SPECS_CQP, "r4_chroma_cqp") for ob in (False, True))
+    design = [(d[0] + len(at.pics),) + tuple(d[1:]) for d in over.info["design"]]
+    return Case("r4_chroma_cqp", at.pics + over.pics, at.refs, info=dict(design=design, at_bound=len(at.pics)))
 
 
 def amplify(p: synth.Picture, k: int) -> None:
@@ -999,13 +1029,20 @@ CLAMP_LINES = [[255, 255, 255, 255, 255, 251, 251, 251], [251, 251, 251, 255, 25
                [255, 255, 255, 255, 254, 250, 250, 250], [0, 0, 0, 0, 1, 5, 5, 5]]
 
 
-def _set_qp(m, qp):
+def qpc_of(qp, off=0):
+    """QPc of 8.5.8 / Table 8-15 for QPY `qp` under chroma_qp_index_offset `off` (-12..12)."""
+    return QP_C[min(51, max(0, int(qp) + int(off)))]
+
+
+def _set_qp(m, qp, offs=(0, 0)):
+    """qp_y and the two chroma QPs it implies under (chroma_qp_index_offset, second_chroma_qp_index_offset)."""
+    assert all(-12 <= o <= 12 for o in offs)
     m["qp_y"], m["qp_scaled"][0] = qp, qp
-    m["qp_c"][:] = QP_C[qp]
-    m["qp_scaled"][1:] = QP_C[qp]
+    for pl in range(2):
+        m["qp_c"][pl] = m["qp_scaled"][1 + pl] = qpc_of(qp, offs[pl])
 
 
-def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
+def build_d(L, kind: str, horizontal: bool, grids, name: str, idc: int = 1, structures=None) -> Case:
     """Pictures whose samples before the loop filter are known by construction: every MB is an inter
     MB with zero motion (it copies the crafted plane held by every DPB slot, minus the flat
     residual of its DC-only coded blocks) or an I_PCM MB (its samples are the crafted plane's), and
@@ -1020,17 +1057,43 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
       coded blocks' inner edges) off; QP up to 36 (alpha <= 50).
     kind "pcm": I_PCM MBs (QP 0) between inter MBs: bS 4 on the MB edges, the strong filter's
       thresholds.
-    grids: per picture (FilterOffsetA, FilterOffsetB, QP per logical MB [rows][columns])."""
+    grids: per picture (FilterOffsetA, FilterOffsetB, QP per logical MB [rows][columns]) and, for the
+    cases of tests/extremes_d2.py, the chroma QP offsets (Cb, Cr) and the picture's own kind.
+    idc 3 (4:4:4): Cb and Cr are full-size planes whose lines are luma_designs under each plane's own
+    alpha / beta.  structures: per picture A.FRAME or a field parity; a field picture's crafted planes
+    sit in its own parity's rows of the two DPB frames (the other parity's field would be read with a
+    chroma offset), and its horizontal intra MB edges have bS 3."""
     Wl, Hl = (3, 5) if horizontal else (5, 3)
     quant = O.quant_flat()[0]
-    pics, lines, refs_all = [], [], None
-    for pi, (offa, offb, grid) in enumerate(grids):
+    pics, lines, refs_all, design = [], [], None, []
+    kind0 = kind
+    cm = 16 if idc == 3 else 8              # chroma samples per MB, along both axes
+    for pi, g in enumerate(grids):
+        offa, offb, grid = g[:3]
+        offs = g[3] if len(g) > 3 else (0, 0)
+        kind = g[4] if len(g) > 4 else kind0
+        structure = structures[pi % len(structures)] if structures else A.FRAME
+        fld = structure != A.FRAME
+        assert not (idc == 3 and (kind == "mix" or fld)) and not (fld and kind == "mix")
         # one DPB for the case: picture pi's crafted plane sits in slots 2 pi and 2 pi + 1
-        cfg = synth.default_cfg(L, 3, 5, 3, num_refs=2 * len(grids), filter_offset_a=offa, filter_offset_b=offb)
+        over = dict(num_refs=2 * len(grids), filter_offset_a=offa, filter_offset_b=offb)
+        if idc == 3:
+            over["chroma_format"] = 3
+        if fld:
+            over.update(structure=structure, num_refs=4 * len(grids))       # fields: 2 len(grids) frames
+        cfg = synth.default_cfg(L, 3, 5, 3, **over)
         p = synth.picture(L, cfg, pi)
-        entry = [[int(v) for v in p.slices["ref_slot"][0][0]].index(s) for s in (2 * pi, 2 * pi + 1)]
+        if fld:
+            par = A.REF_BOTTOM if structure == A.BOTTOM_FIELD else 0
+            for sl in p.slices:
+                sl["ref_slot"][:] = -1
+                sl["ref_slot"][0][:2] = [2 * pi | par, (2 * pi + 1) | par]
+                sl["num_ref"][0] = 2
+            entry = [0, 1]
+        else:
+            entry = [[int(v) for v in p.slices["ref_slot"][0][0]].index(s) for s in (2 * pi, 2 * pi + 1)]
         Y = np.full((16 * Hl, 16 * Wl), 128, np.int64)
-        C = [np.full((8 * Hl, 8 * Wl), 128, np.int64) for _ in range(2)]
+        C = [np.full((cm * Hl, cm * Wl), 128, np.int64) for _ in range(2)]
         res = np.zeros_like(Y)                     # residual of the coded blocks
         mbs = np.zeros((Hl, Wl), A.MB_DTYPE)
         ref8 = np.zeros((2 * Hl, 2 * Wl), np.int8)
@@ -1041,12 +1104,12 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
             for cx in range(Wl):
                 m = mbs[cy, cx]
                 m["mb_type"] = A.P_16x16
-                _set_qp(m, int(grid[cy][cx]))
+                _set_qp(m, int(grid[cy][cx]), offs)
                 ref8[2 * cy:2 * cy + 2, 2 * cx:2 * cx + 2] = cx & 1 if kind != "pcm" else 0
                 if kind == "pcm" and cx & 1:
                     pcm[cy, cx] = True
                     m["mb_type"], m["flags"], m["cbp_blks"] = A.I_PCM, A.MBF_INTRA, 0xFFFF
-                    _set_qp(m, 0)
+                    _set_qp(m, 0, offs)
         # the bS of each 4-line segment of each vertical MB edge
         seg_bs = np.zeros((4 * Hl, Wl), np.int64)
         for cy in range(Hl):
@@ -1054,7 +1117,7 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
                 if kind == "bs1":
                     seg_bs[4 * cy:4 * cy + 4, cx] = 1
                 elif kind == "pcm":
-                    seg_bs[4 * cy:4 * cy + 4, cx] = 4
+                    seg_bs[4 * cy:4 * cy + 4, cx] = 3 if fld and horizontal else 4
                 else:
                     pat = [(0, 1, 2), (1, 2, 0), (2, 0, 1), (0, 2, 1), (1, 0, 2), (2, 1, 0)][(cx + 2 * cy + pi) % 6]
                     pat = [pat[0], pat[1], pat[2], pat[(cx + cy) % 3]]
@@ -1107,8 +1170,8 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
                 lines.append(dict(pic=pi, plane=0, edge=x, at=yy, bS=bS, alpha=alpha, beta=beta, tc0=tc0, line=line))
             for pl in range(2):
                 n_line = 0
-                for yc in range(8 * Hl):
-                    cy, seg = yc // 8, yc // 2
+                for yc in range(cm * Hl):
+                    cy, seg = yc // cm, yc * (16 // cm) // 4
                     bS = int(seg_bs[seg, cx])
                     mp, mq = mbs[cy, cx - 1], mbs[cy, cx]
                     qpav = (int(mp["qp_c"][pl]) + int(mq["qp_c"][pl]) + 1) >> 1
@@ -1119,18 +1182,21 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
                     base, sgn = (235, -1) if hi else (20, 1)
                     if not banded:
                         base, sgn = ((20, 1), (235, -1), (90, 1), (170, -1))[(yc + cx + pl) % 4]
-                    ds = chroma_designs(alpha, beta, base, sgn)
-                    if not banded:
-                        ds += [c[2:6] for c in CLAMP_LINES]
+                    if idc == 3:
+                        ds = luma_designs(alpha, beta, bS if bS else 1, base, sgn) + CLAMP_LINES
                     else:
-                        ds = [d for d in ds if (min(d) >= 175 if hi else max(d) <= 80)]
-                    line = ds[(yc % 8 + 8 * ((pi + cx + cy + pl) % 3)) % len(ds)] if ds else [base] * 4
+                        ds = chroma_designs(alpha, beta, base, sgn)
+                        if not banded:
+                            ds += [c[2:6] for c in CLAMP_LINES]
+                        else:
+                            ds = [d for d in ds if (min(d) >= 175 if hi else max(d) <= 80)]
+                    line = ds[(yc % cm + cm * ((pi + cx + cy + pl) % 3)) % len(ds)] if ds else [base] * 4
                     n_line += 1
-                    C[pl][yc, 8 * cx - 2:8 * cx + 2] = line
+                    C[pl][yc, cm * cx - len(line) // 2:cm * cx + len(line) // 2] = line
                     if banded:
                         C[pl][yc, 8 * cx - 4:8 * cx - 2] = line[0]
                         C[pl][yc, 8 * cx + 2:8 * cx + 4] = line[3]
-                    lines.append(dict(pic=pi, plane=1 + pl, edge=8 * cx, at=yc, bS=bS, alpha=alpha, beta=beta, tc0=tc0,
+                    lines.append(dict(pic=pi, plane=1 + pl, edge=cm * cx, at=yc, bS=bS, alpha=alpha, beta=beta, tc0=tc0,
                                       line=line))
         if banded:          # the MBs' first and last columns lie in no line: give them their band too
             for yy in range(16 * Hl):
@@ -1165,7 +1231,7 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
                 m["coef_off"] = sum(len(a) for a in pool)
                 if pcm[cy, cx]:
                     raw = np.concatenate([T(Y[16 * cy:16 * cy + 16, 16 * cx:16 * cx + 16]).ravel()] +
-                                         [T(C[pl][8 * cy:8 * cy + 8, 8 * cx:8 * cx + 8]).ravel() for pl in range(2)])
+                                         [T(C[pl][cm * cy:cm * cy + cm, cm * cx:cm * cx + cm]).ravel() for pl in range(2)])
                     pool.append(raw.astype(np.uint8).view(np.int16))
                 else:
                     cb = coded[4 * cy:4 * cy + 4, 4 * cx:4 * cx + 4]
@@ -1185,7 +1251,7 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
                     m["cbp"], m["cbp_blks"] = cbp, blks
                 recs[py * W + px] = m
         p.mbs[:] = recs
-        p.levels = np.concatenate(pool + [np.zeros(8, np.int16)])
+        p.levels = np.concatenate(pool + [np.zeros(8 + (128 if idc == 3 else 0), np.int16)])     # (4:4:4: include/h264r.h)
         p.mv[:] = 0
         p.ref_idx[0] = np.array(entry, np.int8)[T(ref4)]
         p.ref_idx[1] = -1
@@ -1195,6 +1261,11 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
         check_bounds(p)
         planes = tuple(T(a).astype(np.uint8) for a in (Y - res, C[0], C[1]))
         want = tuple(T(a).astype(np.uint8) for a in (Y, C[0], C[1]))
+        if fld:                 # the crafted field in its parity's rows of two DPB frames, poison in the other rows
+            frames = tuple(np.full((2 * a.shape[0], a.shape[1]), 77, np.uint8) for a in planes)
+            for f, a in zip(frames, planes):
+                f[int(structure == A.BOTTOM_FIELD)::2] = a
+            planes = frames
         if refs_all is None:
             refs_all = [tuple(np.zeros_like(a) for a in planes) for _ in range(2 * len(grids))]
         refs_all[2 * pi] = refs_all[2 * pi + 1] = planes
@@ -1202,8 +1273,11 @@ def build_d(L, kind: str, horizontal: bool, grids, name: str) -> Case:
         for k in range(3):
             assert np.array_equal(got[k], want[k]), f"{name}[{pi}] plane {k}: the reconstruction is not the crafted plane"
         pics.append(p)
+        qy = p.mbs["qp_y"].reshape(H, W).astype(np.int64)
+        design.append(dict(want=want, qp_y=qy, qp_c=[p.mbs["qp_c"][:, pl].reshape(H, W).astype(np.int64) for pl in range(2)],
+                           offa=offa, offb=offb, offs=offs, kind=kind, structure=structure))
     # a line's position in the picture's planes: `edge` along x (vertical edges) or along y
-    return Case(name, pics, refs_all, info=dict(lines=lines, horizontal=horizontal))
+    return Case(name, pics, refs_all, chroma_format=idc, info=dict(lines=lines, horizontal=horizontal, design=design))
 
 
 # FilterOffsetA / B and the QP of each logical MB [rows][columns]: indexA 16 (the first non-zero alpha),
@@ -1360,14 +1434,36 @@ def one_mb(p: synth.Picture, mi: int) -> synth.Picture:
 
 
 # ---------------------------------------------------------------- D, every edge: inner edges, bS 3, Intra_16x16, 8x8 transform
-def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None, probe=None):
+def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None, probe=None, idc=1, wrong=()):
     """8.7 on a whole picture given the bS of every edge segment, in Python integers: per MB in raster
-    order the vertical edges left to right, then the horizontal ones, luma and (edges 0 and 2) chroma.
-    planes: [Y, Cb, Cr] int arrays, filtered in place.  qp_y / qp_c [H][W]; bsV[by][bx] the bS of the
-    vertical edge left of 4x4 block (bx, by), bsH[by][bx] of the horizontal edge above it (0: not
-    filtered).  log(plane, vertical, inner, mb, bS, alpha, beta, tc0, line before): one call per line.
+    order the vertical edges left to right, then the horizontal ones, luma and chroma.
+    planes: [Y, Cb, Cr] int arrays, filtered in place.  qp_y [H][W]; qp_c [H][W], or one such grid per
+    chroma plane; bsV[by][bx] the bS of the vertical edge left of 4x4 block (bx, by), bsH[by][bx] of the
+    horizontal edge above it (0: not filtered).
+    idc, the chroma geometry: 1 (4:2:0) an MB's chroma is 8 x 8, edges 0 and 2 of either direction at
+    chroma offsets 0 and 4, a line taking the bS of the luma line twice as far along the edge; 2
+    (4:2:2) 8 wide and 16 high: vertical edges at columns 0 and 4 of 16 lines each, line y under the bS
+    of luma row y >> 2 of luma edges 0 and 2, and FOUR horizontal edges at rows 0, 4, 8, 12, edge e
+    under bsH of luma edge e at luma column 2 x; 3 (4:4:4) Cb and Cr are filtered as luma is, on every
+    luma edge with the luma's bS, under alpha / beta of their own QPs.
+    log(plane, vertical, inner, mb, bS, alpha, beta, tc0, line before): one call per line.
     probe(plane, vertical, (x, y) of q0, bS, alpha, beta, indexA, line before): one call per line of
-    every edge the walk meets, those of bS 0 included."""
+    every edge the walk meets, those of bS 0 included.
+    wrong: names of deliberate mistakes, for the mutation checks of tests/test_extremes.py:
+    "swap_planes" (Cb under Cr's QP and the reverse), "qpc_from_qpy" (both planes under QP_C[qp_y]),
+    "q_side_qp" (the q side's QP instead of the average), "422_v_row_half" (4:2:2 vertical chroma bS
+    from luma row y >> 1), "422_h_drop" (4:2:2 chroma rows 4 and 12 not filtered), "444_chroma_filter"
+    (4:4:4 Cb / Cr through the chroma filter)."""
+    qp_c = np.asarray(qp_c)
+    qp_c = [qp_c, qp_c] if qp_c.ndim == 2 else [qp_c[0], qp_c[1]]
+    cw, ch = {1: (8, 8), 2: (8, 16), 3: (16, 16)}[idc]
+
+    def qp_at(pl, y, x):
+        if pl == 0:
+            return int(qp_y[y][x])
+        if "qpc_from_qpy" in wrong:
+            return QP_C[int(qp_y[y][x])]
+        return int(qp_c[2 - pl if "swap_planes" in wrong else pl - 1][y][x])
     for my in range(H):
         for mx in range(W):
             for vertical in (True, False):
@@ -1376,23 +1472,31 @@ def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None, pr
                         continue
                     px, py = (mx - (e == 0), my) if vertical else (mx, my - (e == 0))
                     for pl in range(3):
-                        if pl and e & 1:
+                        like_luma = pl == 0 or idc == 3
+                        four = idc == 2 and pl and not vertical         # 4:2:2: a chroma edge per luma edge
+                        if not like_luma and e & 1 and not (four and "422_h_drop" not in wrong):
                             continue
-                        qq = qp_y if pl == 0 else qp_c
-                        qpav = (int(qq[py][px]) + int(qq[my][mx]) + 1) >> 1
+                        qpav = (qp_at(pl, py, px) + qp_at(pl, my, mx) + 1) >> 1
+                        if "q_side_qp" in wrong:
+                            qpav = qp_at(pl, my, mx)
                         ia, ib = min(51, max(0, qpav + offa)), min(51, max(0, qpav + offb))
-                        n, size, pos = (4, 16, 4 * e) if pl == 0 else (2, 8, 2 * e)
+                        mw, mh = (16, 16) if like_luma else (cw, ch)
+                        n = 4 if like_luma else 2
+                        pos = 4 * e if like_luma or four else 2 * e
+                        size = mh if vertical else mw
                         img = planes[pl]
                         for k in range(size):
-                            seg = (k if pl == 0 else 2 * k) // 4
+                            seg = k * 16 // size // 4
+                            if idc == 2 and pl and vertical and "422_v_row_half" in wrong:
+                                seg = (k >> 1) & 3
                             bS = int(bsV[4 * my + seg][4 * mx + e]) if vertical else int(bsH[4 * my + e][4 * mx + seg])
                             if not bS and probe is None:
                                 continue
                             if vertical:
-                                y, x = size * my + k, size * mx + pos
+                                y, x = mh * my + k, mw * mx + pos
                                 line = [int(v) for v in img[y, x - n:x + n]]
                             else:
-                                y, x = size * my + pos, size * mx + k
+                                y, x = mh * my + pos, mw * mx + k
                                 line = [int(v) for v in img[y - n:y + n, x]]
                             if probe:
                                 probe(pl, vertical, (x, y), bS, ALPHA[ia], BETA[ib], ia, line)
@@ -1401,7 +1505,10 @@ def deblock_restate(planes, W, H, qp_y, qp_c, bsV, bsH, offa, offb, log=None, pr
                             tc0 = TC0[ia][bS - 1] if bS < 4 else 0
                             if log:
                                 log(pl, vertical, e > 0, (mx, my), bS, ALPHA[ia], BETA[ib], tc0, line)
-                            out = filter_line(line, ALPHA[ia], BETA[ib], bS, pl > 0, tc0)
+                            if idc == 3 and pl and "444_chroma_filter" in wrong:
+                                out = line[:2] + filter_line(line[2:6], ALPHA[ia], BETA[ib], bS, True, tc0) + line[6:]
+                            else:
+                                out = filter_line(line, ALPHA[ia], BETA[ib], bS, not like_luma, tc0)
                             if vertical:
                                 img[y, x - n:x + n] = out
                             else:
@@ -1416,7 +1523,7 @@ D_KINDS = "IPTIP"
 D_EVERY = [(0, 0, 44, 51), (0, 0, 28, 40), (6, -6, 16, 30), (-12, 12, 40, 51), (12, -12, 30, 45), (12, 6, 44, 51)]
 
 
-def build_d_every(L, horizontal: bool) -> Case:
+def build_d_every(L, horizontal: bool, name=None, offs=None, idc: int = 1) -> Case:
     """Threshold lines on EVERY luma and chroma edge of the filter direction, inner ones included, in
     pictures mixing: P_8x8 MBs whose 8x8 columns alternate between two DPB slots with identical planes
     (bS 1 on MB edges and on the inner 8x8 edge) and DC-only coded 4x4 blocks (bS 2, any QP);
@@ -1428,19 +1535,30 @@ def build_d_every(L, horizontal: bool) -> Case:
     and |q1 - q0| take 0, beta - 1, beta.  The edges of the other direction are filtered too, on
     whatever the rows hold: the census restates the whole loop filter (deblock_restate) from the
     designed bS of every segment.  Logical picture, transposed for horizontal edges (the prediction
-    is then horizontal)."""
+    is then horizontal).
+    The cases of tests/extremes_d2.py: offs, per picture the chroma QP offsets (Cb, Cr), each chroma
+    plane crafted on the thresholds of its own QPc; idc 2 (4:2:2: no 8x8 transform, its MBs become
+    P_8x8 ones; an MB's chroma is 8 x 16, so a horizontal case has four chroma edges per MB) and idc 3
+    (4:4:4: Cb and Cr crafted like luma; the coded blocks' levels are luma's alone)."""
     Wl, Hl = (3, 5) if horizontal else (5, 3)
     W, H = 5, 3
     pics, refs_all, design = [], None, []
+    # an MB's chroma in the logical picture: (cells of 4 samples along x, rows)
+    ccell, crow = {1: (2, 8), 2: (4, 8) if horizontal else (2, 16), 3: (4, 16)}[idc]
     for pi, (offa, offb, qlo, qhi) in enumerate(D_EVERY):
-        cfg = synth.default_cfg(L, 3, W, H, num_refs=2 * len(D_EVERY), filter_offset_a=offa, filter_offset_b=offb,
-                                transform8x8=1)
+        co = offs[pi] if offs else (0, 0)
+        over = dict(num_refs=2 * len(D_EVERY), filter_offset_a=offa, filter_offset_b=offb, transform8x8=int(idc != 2))
+        if idc != 1:
+            over["chroma_format"] = idc
+        cfg = synth.default_cfg(L, 3, W, H, **over)
         p = synth.picture(L, cfg, pi)
         entry = [[int(v) for v in p.slices["ref_slot"][0][0]].index(s) for s in (2 * pi, 2 * pi + 1)]
         kind = [[(D_KINDS0[(cx + pi) % 5] if cy == 0 else D_KINDS[(cx + cy + pi) % 5]) for cx in range(Wl)] for cy in range(Hl)]
+        if idc == 2:
+            kind = [[("P" if k == "T" else k) for k in row] for row in kind]
         qp = np.array([[0 if kind[cy][cx] == "C" else qlo + (7 * cx + 5 * cy + 3 * pi) % (qhi - qlo + 1)
                         for cx in range(Wl)] for cy in range(Hl)])
-        qpc = np.array([[QP_C[v] for v in row] for row in qp])
+        qpc = [np.array([[qpc_of(v, co[pl]) for v in row] for row in qp]) for pl in range(2)]
         intra = np.array([[k in "IC" for k in row] for row in kind])
         ref4 = np.zeros((4 * Hl, 4 * Wl), np.int64)
         coded = np.zeros((4 * Hl, 4 * Wl), bool)
@@ -1474,10 +1592,8 @@ def build_d_every(L, horizontal: bool) -> Case:
                 if by:
                     bsH[by, bx] = bs_of((by, bx), (by - 1, bx), by % 4 == 0, t8 and by % 2 == 1, t8 and by % 4 != 0)
         # the crafted planes: rows of 4-sample cells [c + a, c, c, c + b]
-        def craft(width_cells, rows, qq, chroma):
+        def craft(width_cells, rows, qq, per_mb, mbh):
             out = np.zeros((rows, 4 * width_cells), np.int64)
-            per_mb = 2 if chroma else 4
-            mbh = 8 if chroma else 16
 
             def edge_ab(cyq, k):                        # alpha, beta of the edge left of cell k
                 qpav = (int(qq[cyq][(k - 1) // per_mb]) + int(qq[cyq][k // per_mb]) + 1) >> 1
@@ -1519,14 +1635,15 @@ def build_d_every(L, horizontal: bool) -> Case:
                     out[y, 4 * k:4 * k + 4] = (c + a, c, c, c + b)
                     b_prev = b
             return np.clip(out, 0, 255)
-        Y = craft(4 * Wl, 16 * Hl, qp, False)
-        C = [craft(2 * Wl, 8 * Hl, qpc, True) + d for d in (0, 3)]
+        Y = craft(4 * Wl, 16 * Hl, qp, 4, 16)
+        C = [craft(ccell * Wl, crow * Hl, qpc[pl], ccell, crow) + d for pl, d in enumerate((0, 3))]
+        cwl = 4 * ccell
         for cy in range(1, Hl):                       # Intra_16x16 vertical: the row above, 16 times
             for cx in range(Wl):
                 if kind[cy][cx] == "I":
                     Y[16 * cy:16 * cy + 16, 16 * cx:16 * cx + 16] = Y[16 * cy - 1, 16 * cx:16 * cx + 16]
                     for pl in range(2):
-                        C[pl][8 * cy:8 * cy + 8, 8 * cx:8 * cx + 8] = C[pl][8 * cy - 1, 8 * cx:8 * cx + 8]
+                        C[pl][crow * cy:crow * cy + crow, cwl * cx:cwl * cx + cwl] = C[pl][crow * cy - 1, cwl * cx:cwl * cx + cwl]
         # realise (transposed for horizontal edges)
         T = (lambda a: np.ascontiguousarray(a.T)) if horizontal else (lambda a: np.ascontiguousarray(a))
         pool, recs = [], np.zeros(W * H, A.MB_DTYPE)
@@ -1534,12 +1651,13 @@ def build_d_every(L, horizontal: bool) -> Case:
             for cx in range(Wl):
                 m = np.zeros(1, A.MB_DTYPE)[0]
                 k = kind[cy][cx]
-                _set_qp(m, int(qp[cy, cx]))
+                _set_qp(m, int(qp[cy, cx]), co)
                 m["coef_off"] = sum(len(a) for a in pool)
+                n0 = len(pool)
                 if k == "C":
                     m["mb_type"], m["flags"], m["cbp_blks"] = A.I_PCM, A.MBF_INTRA, 0xFFFF
                     raw = np.concatenate([T(Y[16 * cy:16 * cy + 16, 16 * cx:16 * cx + 16]).ravel()] +
-                                         [T(C[pl][8 * cy:8 * cy + 8, 8 * cx:8 * cx + 8]).ravel() for pl in range(2)])
+                                         [T(C[pl][crow * cy:crow * cy + crow, cwl * cx:cwl * cx + cwl]).ravel() for pl in range(2)])
                     pool.append(raw.astype(np.uint8).view(np.int16))
                 elif k == "I":
                     m["mb_type"], m["flags"] = A.I_16x16, A.MBF_INTRA
@@ -1567,10 +1685,12 @@ def build_d_every(L, horizontal: bool) -> Case:
                                     blks |= 1 << (((q >> 1) * 2 + (b4 >> 1)) * 4 + (q & 1) * 2 + (b4 & 1))
                         pool.append(lv)
                     m["cbp"], m["cbp_blks"] = cbp, blks
+                if idc == 3 and k != "C":              # Cb and Cr blocks like the luma one, all levels zero
+                    pool += [np.zeros(len(a), np.int16) for a in pool[n0:]] * 2
                 px, py = (cy, cx) if horizontal else (cx, cy)
                 recs[py * W + px] = m
         p.mbs[:] = recs
-        p.levels = np.concatenate(pool + [np.zeros(8, np.int16)])
+        p.levels = np.concatenate(pool + [np.zeros(8 + (128 if idc == 3 else 0), np.int16)])
         p.mv[:] = 0
         p.ref_idx[0] = np.array(entry, np.int8)[T(np.repeat(np.repeat(ref4, 1, 0), 1, 1))]
         p.ref_idx[1] = -1
@@ -1596,10 +1716,11 @@ def build_d_every(L, horizontal: bool) -> Case:
                                                      np.argwhere(got[k] != want[k])[:4], kind)
         pics.append(p)
         Tq = (lambda a: np.ascontiguousarray(np.asarray(a).T)) if horizontal else (lambda a: np.asarray(a))
-        design.append(dict(want=want, qp_y=Tq(qp), qp_c=Tq(qpc), offa=offa, offb=offb,
+        design.append(dict(want=want, qp_y=Tq(qp), qp_c=[Tq(qpc[0]), Tq(qpc[1])], offa=offa, offb=offb, offs=co,
                            bsV=Tq(bsH) if horizontal else bsV, bsH=Tq(bsV) if horizontal else bsH,
                            kind=[[kind[cx][cy] for cx in range(Hl)] for cy in range(Wl)] if horizontal else kind))
-    return Case("d_every_" + ("h" if horizontal else "v"), pics, refs_all, info=dict(design=design, horizontal=horizontal))
+    return Case(name or "d_every_" + ("h" if horizontal else "v"), pics, refs_all, chroma_format=idc,
+                info=dict(design=design, horizontal=horizontal))
 
 
 CASES["d_every_v"] = lambda L: build_d_every(L, False)
@@ -1619,3 +1740,11 @@ import extremes_i as _I  # noqa: E402
 
 CASES.update(_I.I_CASES)
 I_CASES = list(_I.I_CASES)
+
+# ---------------------------------------------------------------- D2: deblocking thresholds, per-plane chroma QP and other formats
+import extremes_d2 as _D2  # noqa: E402
+
+CASES.update(_D2.D2_CASES)
+D2_CASES = list(_D2.D2_CASES)
+CASES["r4_chroma_cqp"] = build_r_chroma_cqp       # family R; after the others: tests/golden/extremes.json only grows
+CASES.update(_D2.D2_X_CASES)

@@ -2,7 +2,9 @@
 """Generate tests/golden/extremes.json from the compiled REFERENCE decoder: the directed
 extreme-value cases of tests/extremes.py (residuals at the packed transforms' bound, 0 / 255
 reference patterns, motion vectors at the limits and across every border, extreme explicit
-weights, deblocking lines on the thresholds, strength from motion, directed intra prediction).
+weights, deblocking lines on the thresholds, strength from motion, directed intra prediction, the
+thresholds again under per-plane chroma QPs, in 4:2:2, 4:4:4, field pictures and MBAFF frames).
+New cases are appended to X.CASES: the entries already in the file come out unchanged.
 
 Run where the reference sources are (the GPU box never has them):
 

@@ -18,7 +18,9 @@ import pytest
 
 import _oracle as O
 import extremes as X
+import extremes_d2 as D2
 import extremes_i as I
+import extremes_s as S
 from h264r import _abi as A
 from h264r import synth
 
@@ -168,6 +170,55 @@ def test_census_r_chroma(quant):
         tops.add((cbpc, max(sums[pi][w][4])))
     assert (2, X.PK_RES_MAX + 1) in tops and {k for k, _ in tops} == {1, 2}, tops
     assert all(v <= X.PK_RES_MAX + 16 for _, v in tops), tops
+
+
+def test_census_r_chroma_cqp(quant):
+    """The chroma measure with Cb and Cr dequantised at different QPs (qp_scaled[1] != qp_scaled[2] in
+    every MB): each designed MB has one plane at the bound (over the bound in the designed MB of an
+    over-bound wave) and the other far below it -- the measure of the MB with its heavy plane's
+    levels zeroed stays under 100 -- so a wave's path is decided by the heavy plane's own scales.
+    Packed waves at exactly 32700 and fallback waves occur with the heavy plane being Cb and being Cr,
+    at 32701 exactly where the plane's scales reach it."""
+    c = X.build("r4_chroma_cqp")
+    n_at = c.info["at_bound"]
+    design = {(pi, w): big for pi, w, _, big in c.info["design"]}
+    seen, tops = set(), set()
+    assert {tuple(int(v) for v in m["qp_scaled"][1:]) for p in c.pics for m in p.mbs if int(m["mb_type"]) != A.I_PCM} == {(0, 7), (7, 0)}
+    for pi, p in enumerate(c.pics):
+        assert all(int(m["qp_scaled"][1]) != int(m["qp_scaled"][2]) and [int(v) for v in m["qp_c"]] == [int(v) for v in m["qp_scaled"][1:]]
+                   for m in p.mbs)
+        paths = X.wave_paths(p, quant)
+        heavy = {}
+        for mi, m in enumerate(p.mbs):
+            if int(m["flags"]) & A.MBF_INTRA or not int(m["cbp"]) >> 4:
+                continue
+            _, cac, _, cdc, _ = X.layout(m)
+            o = int(m["coef_off"])
+            span = [[(o + cdc + 4 * pl, 4)] + ([(o + cac + 64 * pl, 64)] if cac is not None else []) for pl in range(2)]
+            mass = [sum(int(np.abs(p.levels[a:a + n].astype(np.int64)).sum()) for a, n in span[pl]) for pl in range(2)]
+            big = int(mass[1] > mass[0])
+            assert max(mass) > 50 * min(mass)
+            top = max(X.wave_sums(X.one_mb(p, mi), quant)[0][4])
+            light = synth.Picture(p.cfg, p.index, p.mbs[mi:mi + 1], p.levels.copy(), p.mv, p.ref_idx, p.slices, p.pic)
+            for a, n in span[big]:
+                light.levels[a:a + n] = 0
+            assert max(X.wave_sums(light, quant)[0][4]) < 100
+            heavy[mi] = (big, top, int(m["qp_scaled"][1 + big]))
+        for w, (_, cp) in enumerate(paths):
+            mine = [heavy[mi] for mi in range(4 * w, 4 * w + 4) if mi in heavy]
+            if not mine:
+                continue
+            if (pi, w) in design:
+                big, top, q = max(mine, key=lambda t: t[1])
+                assert cp == "fallback" and big == design[(pi, w)] and top > X.PK_RES_MAX
+                assert sum(t > X.PK_RES_MAX for _, t, _ in mine) == 1
+                seen.add(("fallback", big))
+                tops.add((q, top))
+            else:
+                assert cp == "packed" and max(t for _, t, _ in mine) <= X.PK_RES_MAX and pi < n_at
+                seen |= {("packed", big) for big, t, _ in mine if t == X.PK_RES_MAX}
+    assert seen == {(k, pl) for k in ("packed", "fallback") for pl in (0, 1)}, seen
+    assert (0, X.PK_RES_MAX + 1) in tops and all(t <= X.PK_RES_MAX + 16 for _, t in tops), tops
 
 
 @pytest.mark.parametrize("name", ["r5_amplified_intra", "r5_amplified_b", "x_mbaff_p", "x_422_p"])
@@ -410,6 +461,289 @@ def test_census_d_every_edge(name):
             if bx % 4:
                 pairs |= {frozenset((int(bs[by, bx]), int(bs[by + 1, bx]))) for by in range(bs.shape[0] - 1) if by % 4 != 3}
     assert {frozenset((0, 2)), frozenset((1, 2))} <= pairs, pairs
+
+
+# ---------------------------------------------------------------- census: D2
+def _d2_walk(name):
+    """Per picture of a D2 case: the oracle's reconstruction and output, the restated output, and the
+    lines of every edge of bS > 0 as they stand when the restatement filters them:
+    (picture, plane, vertical, edge of the MB 0..3, bS, alpha, beta, tc0, line, like luma)."""
+    if name not in _d2_walk.done:
+        c = X.build(name)
+        mw = {0: (16, 16), 1: A.chroma_mb(c.chroma_format), 2: A.chroma_mb(c.chroma_format)}
+        pics, lines = [], []
+        for pi, p in enumerate(c.pics):
+            def probe(pl, vertical, xy, bS, alpha, beta, ia, line, pi=pi):
+                if bS:
+                    at = xy[0] % mw[pl][0] if vertical else xy[1] % mw[pl][1]
+                    e = at // (4 if len(line) == 8 or (c.chroma_format == 2 and not vertical) else 2)
+                    lines.append((pi, pl, vertical, e, bS, alpha, beta, X.TC0[ia][bS - 1] if bS < 4 else 0, line, len(line) == 8))
+            planes, bs = D2.restate(c, pi, probe=probe)
+            pics.append((O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs), planes, bs))
+        _d2_walk.done[name] = (pics, lines)
+    return _d2_walk.done[name]
+
+
+_d2_walk.done = {}
+
+
+@pytest.mark.parametrize("name", X.D2_CASES)
+def test_census_d2_restated(name):
+    """Every picture of every D2 case: the reconstruction is the crafted planes, and the oracle's
+    output equals the whole loop filter restated (strengths from the records by
+    extremes_s.strength_restate, the filter by X.deblock_restate with the case's chroma geometry and
+    one QP grid per chroma plane), byte for byte; it changes the luma of every picture and each chroma
+    plane of most (a plane whose indexA stays below 16 is left as it is, while the other plane of the
+    picture is filtered).  A build_d_every case's designed bS of every segment is the restated one."""
+    c = X.build(name)
+    pics, _ = _d2_walk(name)
+    changed = np.zeros((len(pics), 3), bool)
+    for pi, (rec, full, planes, (bsV, bsH)) in enumerate(pics):
+        d = c.info["design"][pi]
+        for k in range(3):
+            assert np.array_equal(rec[k], d["want"][k]), (name, pi, k)
+            assert np.array_equal(planes[k], full[k]), (name, pi, k, np.argwhere(planes[k] != full[k])[:3])
+            changed[pi, k] = not np.array_equal(full[k], rec[k])
+        assert changed[pi, 0] and changed[pi, 1:].any(), (name, pi)
+        if "bsV" in d:
+            assert np.array_equal(bsV, d["bsV"]) and np.array_equal(bsH, d["bsH"]), (name, pi)
+        m = c.pics[pi].mbs
+        for pl in range(2):             # the records are legal: both chroma QPs follow from qp_y and the picture's offsets
+            assert [int(v) for v in m["qp_c"][:, pl]] == [X.qpc_of(q, d["offs"][pl]) for q in m["qp_y"]]
+            assert (m["qp_scaled"][:, 1 + pl] == m["qp_c"][:, pl]).all()
+        assert (m["qp_y"][m["mb_type"] == A.I_PCM] == 0).all()
+    assert (2 * changed.sum(0) > len(pics)).all(), changed
+    offs = [d["offs"] for d in c.info["design"]]
+    assert all(a != b for a, b in offs) and all(offs[i] != offs[i + 1] for i in range(len(offs) - 1)), offs
+    assert all(not np.array_equal(c.info["design"][i]["qp_y"], c.info["design"][i + 1]["qp_y"]) for i in range(len(offs) - 1))
+
+
+@pytest.mark.parametrize("name", D2.D2_LINE_CASES)
+def test_census_d2_lines(name):
+    """Every designed line of the build_d cases, as in test_census_d_lines: the reconstruction holds
+    it, the output holds 8.7.2's filter of it under the designed bS and the PLANE's own alpha, beta and
+    tc0 (4:4:4: the luma filter for Cb and Cr; field pictures: bS 3 on horizontal intra MB edges)."""
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    pics, _ = _d2_walk(name)
+    changed = {0: 0, 1: 0, 2: 0}
+    for ln in c.info["lines"]:
+        rec, full = pics[ln["pic"]][:2]
+        chroma = len(ln["line"]) == 4
+        assert chroma == (ln["plane"] > 0 and c.chroma_format != 3)
+        assert _line_samples(rec, ln, hz) == ln["line"]
+        want = X.filter_line(ln["line"], ln["alpha"], ln["beta"], ln["bS"], chroma, ln["tc0"])
+        got = _line_samples(full, ln, hz)
+        assert got == want, (ln, got, want)
+        if not X.classify(ln["line"], ln["alpha"], ln["beta"], ln["bS"], chroma, ln["tc0"])["on"]:
+            assert got == ln["line"]
+        changed[ln["plane"]] += got != ln["line"]
+    assert all(v > 30 for v in changed.values()), changed
+    kinds = {(d["kind"], d["structure"]) for d in c.info["design"]}
+    if name.startswith("d_field"):
+        assert kinds == {(k, s) for k in ("pcm", "bs1") for s in (A.TOP_FIELD, A.BOTTOM_FIELD)}
+        assert {ln["bS"] for ln in c.info["lines"]} == ({1, 3} if hz else {1, 4})
+    else:
+        assert {k for k, _ in kinds} == ({"bs1", "mix", "pcm"} if name.startswith("d_cqp") else {"bs1", "pcm"})
+
+
+@pytest.mark.parametrize("name", ["d_cqp_v", "d_cqp_h"])
+def test_census_d2_cqp_pairs(name):
+    """The offset pairs (-12, +12), (+12, -12), an unequal pair of one sign and a pair (0, k); on every MB
+    edge Cb's and Cr's lines are different designs; and there are MB edges where one plane has
+    indexA < 16 (alpha 0: its samples stay) while the other's lines are filtered, both ways round."""
+    c = X.build(name)
+    offs = [d["offs"] for d in c.info["design"]]
+    assert (-12, 12) in offs and (12, -12) in offs
+    assert any(a != b and a * b > 0 for a, b in offs) and any(a == 0 and b != 0 for a, b in offs)
+    per = {}
+    for ln in c.info["lines"]:
+        if ln["plane"]:
+            per.setdefault((ln["pic"], ln["edge"], ln["at"] // 8), {1: [], 2: []})[ln["plane"]].append(ln)
+    idle = set()
+    for key, both in per.items():
+        assert [ln["line"] for ln in both[1]] != [ln["line"] for ln in both[2]], key
+        for a, b in ((1, 2), (2, 1)):
+            if all(ln["alpha"] == 0 for ln in both[a]) and any(
+                    ln["bS"] and X.classify(ln["line"], ln["alpha"], ln["beta"], ln["bS"], True, ln["tc0"])["on"] for ln in both[b]):
+                idle.add(a)
+    assert idle == {1, 2}, idle
+
+
+def _d2_cells(lines, hz, plane, inner_of=lambda e: e > 0):
+    """{(inner, bS): [(alpha, beta, tc0, classification)]} of one plane's lines across the designed direction."""
+    cells = {}
+    for pi, pl, vertical, e, bS, al, be, tc0, line, luma in lines:
+        if pl == plane and vertical != hz:
+            cells.setdefault((inner_of(e), bS), []).append((al, be, tc0, X.classify(line, al, be, bS, not luma, tc0), luma))
+    return cells
+
+
+def _d2_thresholds(s, bS, what, sides=True):
+    """One cell on its thresholds: a line on and one off; |p0 - q0| at alpha - 1 and at alpha with beta
+    not deciding; |p1 - p0| and |q1 - q0| at beta - 1 and at beta; bS < 4: the delta clipped; luma
+    filter, bS 4: the step on both sides of (alpha >> 2) + 2 and, with sides, ap / aq true and false on
+    either side (build_d_every's cells [c + a, c, c, c + b] have |p2 - p0| == |p1 - p0|, so a line that
+    is on has ap and aq true: the sides are the build_d cases')."""
+    assert any(m[3]["on"] for m in s) and any(not m[3]["on"] for m in s), what
+    th = {m[3]["step"] - m[0] for m in s if m[0] and m[3]["dp1"] < m[1] and m[3]["dq1"] < m[1]}
+    assert {-1, 0} <= th, (what, th)
+    for key in ("dp1", "dq1"):
+        assert {-1, 0} <= {m[3][key] - m[1] for m in s if m[1] > 1}, (what, key)
+    if bS < 4:
+        assert {m[3]["clip"] for m in s if m[3]["on"]} & {-1, 1}, what
+    elif s[0][4]:
+        strong = {(m[3]["step"] < (m[0] >> 2) + 2, m[3]["ap"] < m[1], m[3]["aq"] < m[1]) for m in s if m[3]["on"]}
+        assert {st for st, _, _ in strong} == {False, True} and (True, True, True) in strong, (what, strong)
+        if sides:
+            assert {a for _, a, _ in strong} == {False, True} == {b for _, _, b in strong}, (what, strong)
+
+
+D2_EVERY_BS = {False: {1, 2, 4}, True: {1, 2, 3}}          # MB edges, inner edges
+
+
+@pytest.mark.parametrize("name", D2.D2_EVERY_CASES)
+def test_census_d2_every_edge(name):
+    """The build_d_every cases, per PLANE (Cb and Cr sit on different thresholds): across the designed
+    direction every bS occurs on MB edges (1, 2, 4) and inner edges (1, 2, 3), and every inner cell
+    and every bS 4 cell is on its thresholds (MB edges of bS 1 / 2: the d_cqp / d_bs1 / d_mix cases).
+    4:2:2: the chroma edges a 4:2:0 picture does not have -- rows 4 and 12 (bS 2 and 3; bS 1 needs an
+    8x8 boundary) -- have lines on and off and a clipped delta per row and bS, and are on the alpha
+    and beta thresholds, per plane.  4:4:4: the cells of Cb and Cr
+    are the luma's, strong filter included; an 8x8-transform MB's 4x4 edges are idle in all planes."""
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    _, lines = _d2_walk(name)
+    n, mb4 = 0, []
+    for plane in range(3):
+        cells = _d2_cells(lines, hz, plane)
+        for inner, want in D2_EVERY_BS.items():
+            assert {bS for i, bS in cells if i == inner} == want, (name, plane, inner)
+        for (inner, bS), s in cells.items():
+            if plane and c.chroma_format != 3 and (inner, bS) == (False, 4):
+                # 8 or 16 lines per chroma MB edge and few intra MBs: Cb's and Cr's lines together, as the D
+                # census takes them; each plane has a line on and a line off
+                assert any(m[3]["on"] for m in s) and any(not m[3]["on"] for m in s), (name, plane)
+                mb4 += s
+            elif inner or bS == 4:
+                _d2_thresholds(s, bS, (name, plane, inner, bS), sides=False)
+                n += 1
+    if mb4:
+        _d2_thresholds(mb4, 4, (name, "Cb + Cr", False, 4))
+        n += 1
+    if c.chroma_format == 2 and hz:
+        for plane in (1, 2):
+            odd = []
+            for e in (1, 2, 3):
+                cells = _d2_cells(lines, hz, plane, inner_of=lambda x: x == e)
+                assert {bS for i, bS in cells if i} == ({2, 3} if e & 1 else {1, 2, 3}), (plane, e)
+                for bS in (2, 3):
+                    s = cells[(True, bS)]
+                    assert any(m[3]["on"] for m in s) and any(not m[3]["on"] for m in s), (name, plane, e, bS)
+                    assert {m[3]["clip"] for m in s if m[3]["on"]} & {-1, 1}, (name, plane, e, bS)
+                    odd += s if e & 1 else []
+            # rows 4 and 12 alone (two chroma lines per luma block: few lines each), their bS 2 and 3
+            # together (tc0 apart, one filter): on the alpha and beta thresholds
+            _d2_thresholds(odd, 2, (name, plane, "rows 4 and 12"))
+            n += 1
+    if c.chroma_format == 3:
+        assert all(luma for *_, luma in lines)
+        # 8x8-transform MBs: the 4x4 inner edges are not filtered in any plane, though a bS 2 line there would be on
+        skipped_on = [0, 0, 0]
+        for d, (rec, full, _, _) in zip(c.info["design"], _d2_walk(name)[0]):
+            for my, row in enumerate(d["kind"]):
+                for mx, k in enumerate(row):
+                    if k != "T":
+                        continue
+                    for pl in range(3):
+                        q = int((d["qp_y"] if pl == 0 else d["qp_c"][pl - 1])[my][mx])
+                        ia, ib = (min(51, max(0, q + o)) for o in (d["offa"], d["offb"]))
+                        want, out = (rec[pl].T, full[pl].T) if hz else (rec[pl], full[pl])
+                        cy, cx = (mx, my) if hz else (my, mx)
+                        for e in (4, 12):
+                            for y in (3, 4, 12):
+                                sl = (16 * cy + y, slice(16 * cx + e - 4, 16 * cx + e + 4))
+                                assert list(out[sl][3:5]) == list(want[sl][3:5])       # p0, q0: no other edge reaches them
+                                skipped_on[pl] += X.classify(want[sl], X.ALPHA[ia], X.BETA[ib], 2, False, X.TC0[ia][1])["on"]
+        assert all(skipped_on), skipped_on
+    print(f"D2 census {name}: {n} cells required and hit")
+
+
+@pytest.mark.parametrize("name", D2.D2_LINE_CASES)
+def test_census_d2_line_cells(name):
+    """The build_d cases, per plane: MB edges of every bS the case has (d_cqp 1, 2, 4; 4:4:4 1, 4; field
+    pictures 1 and 4 on vertical, 1 and 3 on horizontal edges).  Two cells per plane, as bS 1 .. 3
+    differ in tc0 alone: the normal filter (its bS together on the alpha and beta thresholds; per bS a
+    line on, one off and a clipped delta) and bS 4.  A field picture's bS 3 luma lines reach
+    tc0 + 0, + 1 and + 2."""
+    c = X.build(name)
+    hz = c.info["horizontal"]
+    _, lines = _d2_walk(name)
+    want = {1, 2, 4} if name.startswith("d_cqp") else {1, 4} if name.startswith("d_444") else {1, 3} if hz else {1, 4}
+    n = 0
+    for plane in range(3):
+        cells = _d2_cells(lines, hz, plane)
+        assert {bS for i, bS in cells if not i} == want, (name, plane)
+        normal = []
+        for bS in want:
+            s = cells[(False, bS)]
+            if bS == 4:
+                _d2_thresholds(s, bS, (name, plane, bS))
+                n += 1
+            else:
+                normal += s
+                assert any(m[3]["on"] for m in s) and any(not m[3]["on"] for m in s), (name, plane, bS)
+                assert {m[3]["clip"] for m in s if m[3]["on"]} & {-1, 1}, (name, plane, bS)
+        _d2_thresholds(normal, 1, (name, plane, "normal"))
+        n += 1
+        if 3 in want and plane == 0:
+            assert {m[3]["tc"] - m[2] for m in cells[(False, 3)] if m[3]["on"]} == {0, 1, 2}
+    print(f"D2 census {name}: {n} cells required and hit")
+
+
+@pytest.mark.parametrize("wrong,name", [(w, n) for w, names in D2.WRONG.items() for n in names])
+def test_d2_mutation(wrong, name):
+    """A deliberately wrong restatement differs from the oracle's output on some picture of the case,
+    so the byte comparison of the GPU with the oracle would notice the same slip in a kernel."""
+    c = X.build(name)
+    pics, _ = _d2_walk(name)
+    for pi in range(len(c.pics)):
+        planes, _ = D2.restate(c, pi, wrong=(wrong,))
+        if any(not np.array_equal(planes[k], pics[pi][1][k]) for k in range(3)):
+            return
+    raise AssertionError(f"{name}: the restatement with {wrong} equals the oracle on every picture")
+
+
+def test_census_x_mbaff_cqp():
+    """MBAFF frames with Cb != Cr: frame and field MBs both occur, next to each other in both
+    directions; every record is legal under its picture's offsets.
+    With the deblocking QPs alone made wrong (extremes_d2.with_qpc: Cb's for Cr and the reverse, or
+    QP_C[qp_y] for both) the oracle's reconstruction is the same and its output differs in Cb AND in Cr
+    of every picture, and over the case in frame MBs and in field MBs of either plane: a kernel that
+    reads the other plane's qp_c, or derives it from qp_y, cannot equal the oracle on this case."""
+    c = X.build("x_mbaff_cqp")
+    where = set()
+    for p, offs in zip(c.pics, c.info["offs"]):
+        assert int(p.pic["structure"][0]) == A.MBAFF_FRAME and offs[0] != offs[1]
+        W, H = p.cfg.width_mbs, p.cfg.height_mbs
+        fld = (p.mbs["flags"].reshape(H, W) & A.MBF_FIELD) != 0
+        assert (fld[0::2] == fld[1::2]).all() and (fld[:, 1:] != fld[:, :-1]).any() and (fld[2:] != fld[:-2]).any()
+        for pl in range(2):
+            assert [int(v) for v in p.mbs["qp_c"][:, pl]] == [X.qpc_of(q, offs[pl]) for q in p.mbs["qp_y"]]
+            assert (p.mbs["qp_scaled"][:, 1 + pl] == p.mbs["qp_c"][:, pl]).all()
+        rec, full = O.decode(p, c.refs, stage="recon"), O.decode(p, c.refs)
+        fld_c = np.repeat(np.repeat(fld[0::2], 16, 0), 8, 1)         # chroma samples of field pairs
+        for how in ("swap", "qpy"):
+            q = D2.with_qpc(p, how)
+            assert all(np.array_equal(a, b) for a, b in zip(O.decode(q, c.refs, stage="recon"), rec))
+            other = O.decode(q, c.refs)
+            assert np.array_equal(other[0], full[0])
+            for k in (1, 2):
+                diff = other[k] != full[k]
+                assert diff.any(), (p.index, how, k)
+                where |= {(how, k, f) for f in (False, True) if diff[fld_c == f].any()}
+                print(f"x_mbaff_cqp picture {p.index} {how} plane {k}: {int(diff.sum())} samples differ")
+    assert where == {(how, k, f) for how in ("swap", "qpy") for k in (1, 2) for f in (False, True)}, where
 
 
 # ---------------------------------------------------------------- census: S
@@ -805,3 +1139,139 @@ def test_census_i_mbaff():
             elif int(m["flags"]) & A.MBF_INTRA:
                 assert int(m["cbp"]) == 0 and int(m["cbp_blks"]) == 0
     assert flat == {0, 255}
+
+
+# ---------------------------------------------------------------- census: d_mbaff
+MBAFF_CLASS_BS = {      # the bS an edge class can take in these pictures (intra, coded, frame MB against field MB, else none)
+    "V1": {4, 2}, "V2": {4, 2}, "V3t": {4, 2, 1}, "V3b": {4, 2, 1}, "V4t": {4, 2, 1}, "V4b": {4, 2, 1},
+    "H1": {4, 2}, "H3": {4, 2}, "H2a": {3, 2, 1}, "H2b": {3, 2, 1}, "H4": {3, 2}, "H6": {3, 2},
+    "H5": {3, 2, 1}, "H7": {3, 2, 1}, "Inner-v": {3, 2}, "Inner-h-frame": {3, 2}, "Inner-h-field": {3, 2},
+}
+
+
+def _mbaff_walk():
+    """Per picture of d_mbaff the oracle's output and the restated one, and the restatement's log with the
+    picture index in front: (pi, plane, vertical, class, p MB address, bS, alpha, beta, tc0, line, coords)."""
+    if not _mbaff_walk.done:
+        c = X.build("d_mbaff")
+        for pi, p in enumerate(c.pics):
+            log = []
+            planes = D2.restate_mbaff(c, pi, log=lambda *a: log.append(a))
+            _mbaff_walk.done.append((O.decode(p, c.refs), planes, [(pi,) + a for a in log]))
+    return _mbaff_walk.done
+
+
+_mbaff_walk.done = []
+
+
+def test_census_d_mbaff_restated():
+    """Every picture: MBAFF frame of 4 x 6 MBs, deblock_idc 0 (the last picture's second slice 2), the
+    reconstruction is the crafted planes, and the oracle's output equals deblock_restate_mbaff byte for
+    byte.  The pair kinds hold all four (current, left) and (current, upper) combinations; all four MB
+    kinds occur in frame and in field MBs; the two MBs of every pair differ in qp_y (by 7 or more, so
+    that their averages with a third MB give different alpha), in both qp_c, and in which of their
+    edge blocks are coded;
+    the records are legal."""
+    c = X.build("d_mbaff")
+    kinds = set()
+    for pi, (p, d, (full, planes, _)) in enumerate(zip(c.pics, c.info["design"], _mbaff_walk())):
+        W, H = p.cfg.width_mbs, p.cfg.height_mbs
+        assert (W, H) == (4, 6) and int(p.pic["structure"][0]) == A.MBAFF_FRAME and int(p.pic["constrained_intra_pred"][0]) == 1
+        assert [int(s["deblock_idc"]) for s in p.slices] == ([0, 2] if pi == len(c.pics) - 1 else [0])
+        rec = O.decode(p, c.refs, stage="recon")
+        for k in range(3):
+            assert np.array_equal(rec[k], d["want"][k]), (pi, k)
+            assert np.array_equal(planes[k], full[k]), (pi, k, np.argwhere(planes[k] != full[k])[:4])
+            assert not np.array_equal(full[k], rec[k])
+        f = d["fld"]
+        assert {(bool(f[r, x]), bool(f[r, x - 1])) for r in range(3) for x in range(1, W)} == {(a, b) for a in (False, True) for b in (False, True)}
+        assert {(bool(f[r, x]), bool(f[r - 1, x])) for r in range(1, 3) for x in range(W)} == {(a, b) for a in (False, True) for b in (False, True)}
+        m = p.mbs.reshape(H, W)
+        assert ((m["flags"] & A.MBF_FIELD != 0) == np.repeat(f, 2, 0)).all()
+        for pl in range(2):
+            assert [int(v) for v in p.mbs["qp_c"][:, pl]] == [X.qpc_of(q, d["offs"][pl]) for q in p.mbs["qp_y"]]
+            assert (p.mbs["qp_scaled"][:, 1 + pl] == p.mbs["qp_c"][:, pl]).all()
+        top, bot = m[0::2], m[1::2]
+        assert (np.abs(top["qp_y"].astype(int) - bot["qp_y"]) >= 7).all() and (top["qp_c"] != bot["qp_c"]).all()
+        assert ((top["cbp_blks"] & 0xF99F) != (bot["cbp_blks"] & 0xF99F)).all()          # the blocks along the MB's four edges
+        kinds |= {(str(k), bool(f[y // 2, x])) for y in range(H) for x in range(W) for k in d["kind"][y, x]}
+    assert kinds == {(k, fl) for k in "CPDI" for fl in (False, True)}, kinds
+
+
+def _mbaff_cells():
+    cells = {}
+    for _, _, log in _mbaff_walk():
+        for pi, pl, vertical, cls, pa, bS, al, be, tc0, line, coords in log:
+            if cls == "Inner":
+                cls = "Inner-v" if vertical else "Inner-h-field" if coords[1][0] - coords[0][0] == 2 else "Inner-h-frame"
+            cells.setdefault((cls, pl, bS), []).append((al, be, tc0, X.classify(line, al, be, bS, pl > 0, tc0)))
+    return cells
+
+
+# what the pictures cannot reach, with the reason: (cell, item) -> reason.  Luma alone: an I_PCM MB's chroma QP
+# is QP_C[offset], and its inner chroma edges are live and required wherever that plus the FilterOffset reaches 16.
+_INSIDE_INTRA_LUMA = ("luma bS 3 lies inside an intra MB, and the two intra kinds whose samples are known by construction "
+                      "are I_PCM (qp_y 0: luma indexA <= 12, alpha 0, every line off) and the flat Intra_16x16 DC MB (no "
+                      "step: every line on, nothing to clip)")
+MBAFF_UNREACHABLE = {((cls, 0, 3), item): _INSIDE_INTRA_LUMA for cls in ("Inner-v", "Inner-h-frame", "Inner-h-field")
+                     for item in ("alpha-1", "alpha", "beta-1", "beta", "clip")}
+
+
+def test_census_d_mbaff_cells():
+    """Every (edge class, plane, bS) the rules allow, from the lines as they stand when the restatement
+    filters them: a line on and one off; |p0 - q0| at alpha - 1 and at alpha with beta not deciding;
+    |p1 - p0| or |q1 - q0| at beta - 1 and at beta; bS < 4: the delta clipped at one end at least; luma
+    bS 4: the step on both sides of (alpha >> 2) + 2 with ap / aq true and false.  No class takes a bS
+    outside its set."""
+    cells = _mbaff_cells()
+    req = {(cls, pl, bS) for cls, bss in MBAFF_CLASS_BS.items() for pl in range(3) for bS in bss}
+    assert set(cells) <= req, sorted(set(cells) - req)
+    missing = []
+    for cell in sorted(req):
+        s = cells.get(cell, [])
+        bS, chroma = cell[2], cell[1] > 0
+        on = [m for m in s if m[3]["on"]]
+        need = {"on": bool(on), "off": len(on) < len(s)}
+        th = {m[3]["step"] - m[0] for m in s if m[0] and m[3]["dp1"] < m[1] and m[3]["dq1"] < m[1]}
+        need["alpha-1"], need["alpha"] = -1 in th, 0 in th
+        bt = {m[3][k] - m[1] for m in s if m[1] > 1 for k in ("dp1", "dq1")}
+        need["beta-1"], need["beta"] = -1 in bt, 0 in bt
+        if bS < 4:
+            need["clip"] = bool({m[3]["clip"] for m in on} & {-1, 1})
+        elif not chroma:
+            st = {(m[3]["step"] < (m[0] >> 2) + 2, m[3]["ap"] < m[1], m[3]["aq"] < m[1]) for m in on}
+            need["strong"] = {a for a, _, _ in st} == {False, True} and {b for _, b, _ in st} == {False, True} == {b for _, _, b in st}
+        bad = sorted(k for k, v in need.items() if not v and (cell, k) not in MBAFF_UNREACHABLE)
+        if bad:
+            missing.append((cell, len(s), bad))
+    named = {cell for cell, _ in MBAFF_UNREACHABLE}
+    print(f"d_mbaff census: {len(req)} cells required, {len(req) - len(missing)} hit, of them {len(named)} (luma inner bS 3) on / off only")
+    assert not missing, missing
+
+
+def test_census_d_mbaff_neighbours():
+    """On every V3, V4 and H2 edge the two neighbour MBs gave different (alpha, beta) or a different bS
+    to the luma lines of that one edge, so the choice of neighbour per line or per field edge shows."""
+    edges = {}
+    for _, _, log in _mbaff_walk():
+        for pi, pl, vertical, cls, pa, bS, al, be, tc0, line, coords in log:
+            if pl == 0 and cls[:2] in ("V3", "V4", "H2"):
+                q0 = coords[4]
+                key = (pi, cls[:2], q0[1] // 16, q0[0] // 16 if cls[:2] != "V4" else q0[0] // 32 * 2 + (q0[0] & 1))
+                edges.setdefault(key, {}).setdefault(pa, []).append((al, be, bS))
+    assert len(edges) >= 30
+    for key, by in edges.items():
+        assert len(by) == 2, (key, list(by))
+        a, b = by.values()
+        assert sorted(a) != sorted(b), (key, by)
+
+
+@pytest.mark.parametrize("wrong", D2.WRONG_MBAFF)
+def test_d_mbaff_mutation(wrong):
+    """A deliberately wrong MBAFF restatement differs from the oracle's output on some picture."""
+    c = X.build("d_mbaff")
+    for pi, (full, _, _) in enumerate(_mbaff_walk()):
+        planes = D2.restate_mbaff(c, pi, wrong=(wrong,))
+        if any(not np.array_equal(planes[k], full[k]) for k in range(3)):
+            return
+    raise AssertionError(f"d_mbaff: the restatement with {wrong} equals the oracle on every picture")
