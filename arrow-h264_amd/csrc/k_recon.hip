@@ -11,10 +11,14 @@
 
 using namespace h264r;
 
-// minimum waves per SIMD asked of the register allocator: k_inter4r 4 (<= 128 VGPRs, its
-// natural size with the residual loaded after the motion compensation)
+// minimum waves per SIMD asked of the register allocator: k_inter4r 5 (<= 96 VGPRs).  The plain
+// stages fit them as they are; the generic stages do because they park what is live across the motion
+// compensation without being read by it in LDS (mb_inter4.h Inter4Park) -- never by compiler scratch,
+// which made a 5-wave kernel a third slower (profiles/r06_l_inter_waves5_ab.txt): tests/
+// test_isa_inter_waves5.py holds the kernel to 96 VGPRs, no spill, no scratch, 32 KiB of LDS.
+// 4 builds the same source for 4 waves/SIMD (<= 128 VGPRs).
 #ifndef H264R_INTER_WAVES
-#define H264R_INTER_WAVES 4
+#define H264R_INTER_WAVES 5
 #endif
 // The workgroup's copy of the DPB plane table and of picture `pic`'s slice ref tables, slice
 // types and slice headers.  Every thread issues its loads first (clamped indices, no branch)
@@ -65,7 +69,7 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // k_inter4r: per 16-MB group of a workgroup, first the deblocking records DbInfo of the group's
 // MBs (dbinfo_block: their neighbour records and motion are loaded with the group's own record and
 // motion), then the reconstruction of its inter and I_PCM MBs (inter4_mbs); the records' registers
-// are dead before the motion compensation starts (127 VGPRs with both instantiations below, 4 waves/SIMD).  Round 6 folded the
+// are dead before the motion compensation starts (96 VGPRs with both instantiations below, 5 waves/SIMD).  Round 6 folded the
 // records' own kernel (k_dbinfo, 1.2 ms per 1024 config-3 pictures at 8 waves/SIMD) into it:
 // config 3 11.96 -> 11.78 ms, config 4 4.64 -> 4.53 ms; all-intra config 2 13.87 -> 14.15 ms
 // (its records now run at 4 waves/SIMD; profiles/r06_e_fused_dbinfo_ab.txt).
@@ -87,11 +91,15 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // alone and no weighting (no list loop, no per-list copies and selects, no combine, only the
 // one-list records), every other wave the generic ones.  The workgroup classes its picture
 // from the slice headers its LDS fill holds (inter4_plain_mark); the branch is wave-uniform
-// and its two sides hold their registers apart (124 VGPRs the generic side, 91 the plain one).
-// As a kernel of its own the plain side runs at 5 waves/SIMD and 5.96 instead of 6.48 ms, but each
-// kernel then pays the dispatch of its workgroups for the other kernel's pictures, ~0.9 ns apiece:
-// 0.47 ms for 1024 plain 1080p pictures, 0.12 ms (2.5 % of the step) for config 4's 256, and several
-// pictures per workgroup spilled both kernels (profiles/r09_a_inter_plain_ab.txt).
+// and its two sides hold their registers apart (90 VGPRs the generic side alone, 93 the plain one, 96
+// the kernel, which also keeps 9 SGPRs in the lanes of a VGPR: profiles/r10_a_inter_waves5_isa.txt).
+// Both sides run at 5 waves/SIMD: the generic one parks each list's prediction, list 1's motion word
+// and the MB record in per-lane LDS slots (P below; 18 KiB of the 32 KiB a workgroup may take at 5
+// workgroups per CU) and forms the lane's roles again after the motion compensation; a plain wave
+// executes no parking instruction.  Config 3 kernel_ms.inter 6.24 -> 5.96 ms, configs 4 / 5 2.91 ->
+// 2.79 / 2.80 ms (profiles/r10_a_inter_waves5_ab.txt).  (The plain side as a kernel of its own,
+// k_inter4p, was the first to reach 5 waves but paid the dispatch of its workgroups for the other
+// kernel's pictures: profiles/r09_a_inter_plain_ab.txt)
 extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h264r_batch b, DbInfo* dbinfo, int2 rows,
                                                                                int* sp_flag, uint8_t* recon, int tag,
                                                                                int* zero, int nz, int* zero2, int nz2)
@@ -104,6 +112,7 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
     }
     __shared__ Inter4Lds S;
     __shared__ DbTables T;
+    __shared__ Inter4Park P;
     const int pic = blockIdx.y;
     const Geom g = make_geom(b.width_mbs, b.height_mbs);
     int grp, gend;
@@ -127,15 +136,17 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
         bool done = false;
         // (the one-list records are H264R_INTER_FAST bit 2: without it no wave is a plain one)
         if ((H264R_INTER_FAST & 2) && plain && inter4_plain_wave(pre, nb, ns)) {
-            const uint2 m0 = motion_word<true>(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
+            uint2 m0 = motion_word<true>(pre.mv[0], pre.ri[0], slices, S, pre.q.slice, 0);
+            asm volatile("" : "+v"(m0.y));        // one register across the records, not the two it is formed from
             // (false, with no record written: an empty RefPicList entry -- the generic stages' after all)
             done = (H264R_INTER_DIAG & 32) ||
                    dbinfo_block<true>(b, pic, inter4_lane(g, a0, aend, lane), S, T, pre.q, m0, inter4_no_list(),
                                       slice_hdr<true>(slices, S, pre.q.slice), nb, dbinfo + (size_t)pic * g.nmb, true);
             if (done) {
                 int ln = lane;
-                asm volatile("" : "+v"(ln));
-                inter4_mbs<true>(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+                uint2 mm = m0;
+                asm volatile("" : "+v"(ln), "+v"(mm.x), "+v"(mm.y));
+                inter4_mbs<true>(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag, nullptr, mm);
             }
         }
         if (!done) {
@@ -151,7 +162,7 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
             }
             int ln = lane;
             asm volatile("" : "+v"(ln));
-            inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag);
+            inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag, &P);
         }
         if (++grp >= gend) return;
         a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;

@@ -29,7 +29,8 @@
 // parameters are what it reads and writes: inter4_lane (Inter4Lane, the roles above) -> the gate
 // (invalid / intra / SP / inter4_pcm) -> inter4_predict -> inter4_res_load (Inter4Res) ->
 // inter4_luma_residual (luma_res_bypass / luma_res_4x4 / luma_res_8x8) -> inter4_store_luma ->
-// inter4_chroma_residual -> inter4_store_chroma.  The inter MBs of SP slices are k_inter_sp's:
+// inter4_chroma_residual -> inter4_store_chroma.  The generic instantiation parks state in LDS between
+// the stages (Inter4Park), the PLAIN one does not.  The inter MBs of SP slices are k_inter_sp's:
 // inter4_sp_mbs (mb_inter_sp.h), on the same lane roles, prediction and residual inputs.
 #pragma once
 #include "mb_deblock.h"
@@ -63,6 +64,46 @@ struct Inter4Lds {
     uint8_t slice_type[INTER4_LDS_SLICES];                   // h264r_slice::slice_type of the same slices
     uint8_t not_plain[INTER4_PLAIN_SLICES];                  // slice i keeps the picture from being plain (inter4_plain_picture)
 };
+
+// k_inter4r's parking space for the GENERIC stages: INTER4_PARK_SLOTS dwords per lane that hold state
+// over a motion compensation which does not read it, so that the generic side fits the kernel's
+// register budget (k_recon.hip H264R_INTER_WAVES) without scratch.  Lane-major ([slot][thread]): a
+// wave's 64 lanes touch 64 consecutive dwords, no bank conflict.  A slot is its lane's own, written
+// and read back by the same lane under the same exec mask: no barrier.  The accesses are volatile, so
+// the compiler neither forwards the stored value to the read (that would keep it in a register) nor
+// moves them across each other.
+constexpr int PARK_PRED = 0;     // 2 x 6: each list's prediction (4 luma rows, 2 chroma planes) until the combine
+constexpr int PARK_M1 = 12;      // 2: list 1's motion word while list 0 is compensated
+constexpr int PARK_Q = 14;       // 4: the MB record's dwords 0, 3, 2, 4 (park_put_mb)
+constexpr int INTER4_PARK_SLOTS = 18;
+struct Inter4Park {
+    uint32_t w[INTER4_PARK_SLOTS][256];
+};
+// (address space 3 by name: a volatile access through a generic pointer stays a flat one, 64-bit address and all)
+typedef __attribute__((address_space(3))) volatile uint32_t lds_vdword;
+DEV void park_put(Inter4Park& P, int slot, uint32_t v) { *(lds_vdword*)&P.w[slot][threadIdx.x] = v; }
+DEV uint32_t park_get(Inter4Park& P, int slot) { return *(lds_vdword*)&P.w[slot][threadIdx.x]; }
+// The MB record's dwords that the stages after the motion compensation read (the residual and the
+// slice's weights: mb_type, flags, cbp, slice, qp_scaled, coef_off); the others come back zero (the
+// lossless path reads its prediction modes from the batch, luma_res_bypass).
+constexpr int PARK_Q_N = 4;
+constexpr int PARK_Q_WORD[PARK_Q_N] = {0, 3, 2, 4};            // the chroma residual's first: cbp, flags, qp_scaled
+DEV void park_put_mb(Inter4Park& P, const h264r_mb& q)
+{
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(&q);
+#pragma unroll
+    for (int k = 0; k < PARK_Q_N; ++k) park_put(P, PARK_Q + k, w[PARK_Q_WORD[k]]);
+}
+// FIRST: the first FIRST of those dwords only
+template <int FIRST = PARK_Q_N>
+DEV h264r_mb park_get_mb(Inter4Park& P)
+{
+    h264r_mb q = {};
+    uint32_t* w = reinterpret_cast<uint32_t*>(&q);
+#pragma unroll
+    for (int k = 0; k < FIRST; ++k) w[PARK_Q_WORD[k]] = park_get(P, PARK_Q + k);
+    return q;
+}
 
 // A lane's roles ("Lane roles" above) for the MBs a0 .. a0+3 of a picture.
 struct Inter4Lane {
@@ -762,10 +803,10 @@ DEV void inter4_mc(const Geom& g, const Inter4Lane& L, const Inter4Lds& S, int s
 // bytes; predC[pl]: my 2x2 chroma samples of plane pl (chroma_block_pred2).
 // PLAIN (a plain wave of k_inter4r): the caller's lanes all predict from list 0 alone with default weights, so the
 // prediction is list 0's motion compensation: no list loop, no per-list copies, no combine.
-template <bool PLAIN = false>
+template <bool PLAIN = false, bool PARK = false>
 DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inter4Lane& L, const Inter4Lds& S,
                         const h264r_slice* __restrict__ qs, int wp_mode, uint2 m0, uint2 m1, uint32_t (&predY)[4],
-                        uint32_t (&predC)[2])
+                        uint32_t (&predC)[2], Inter4Park* park = nullptr)
 {
     // a field picture (include/h264r.h H264R_TOP_FIELD) reads fields of the DPB frames:
     // every second row from the field's first row, clamped to the field's own rows
@@ -779,31 +820,62 @@ DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inte
     }
     const int r1 = (int8_t)(m1.y & 255);
     const int dir = (r0 >= 0 && r1 >= 0) ? 2 : (r0 >= 0 ? 0 : 1);
+    if constexpr (PARK) {
+        park_put(*park, PARK_M1, m1.x);
+        park_put(*park, PARK_M1 + 1, m1.y);
+    }
     // the prediction of each list in named registers: an array indexed by the (not
     // unrolled) list loop was promoted to LDS by the compiler (48 B per lane)
     uint32_t pY[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, pC[2][2] = {{0, 0}, {0, 0}};
+    bool parked[2] = {false, false};                                // wave-uniform: list l's prediction is in `park`
 #pragma unroll 1
     for (int l = 0; l < 2; ++l) {
-        const uint2 mw = l ? m1 : m0;
         const int rr = l ? r1 : r0;
         const bool use = rr >= 0;
         if (!__any(use)) continue;                                  // P pictures: list 1 never
+        uint2 mw = l ? m1 : m0;
+        if constexpr (PARK)
+            if (l) mw = make_uint2(park_get(*park, PARK_M1), park_get(*park, PARK_M1 + 1));
         uint32_t tY[4], tC[2];
         inter4_mc(g, L, S, structure, fld, mw, rr, use, tY, tC);
         const bool l1 = l != 0;
+        if constexpr (PARK) {
+            // each list's prediction goes to LDS as it is finished and both come back after the loop:
+            // nothing of either is live across a motion compensation, and the loop carries no
+            // prediction registers (Inter4Park)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            pY[0][i] = (use && !l1) ? tY[i] : pY[0][i];
-            pY[1][i] = (use && l1) ? tY[i] : pY[1][i];
-        }
+            for (int i = 0; i < 4; ++i) park_put(*park, PARK_PRED + 6 * l + i, use ? tY[i] : 0);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            pC[0][k] = (use && !l1) ? tC[k] : pC[0][k];
-            pC[1][k] = (use && l1) ? tC[k] : pC[1][k];
+            for (int k = 0; k < 2; ++k) park_put(*park, PARK_PRED + 6 * l + 4 + k, use ? tC[k] : 0);
+            parked[0] |= !l1;
+            parked[1] |= l1;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                pY[0][i] = (use && !l1) ? tY[i] : pY[0][i];
+                pY[1][i] = (use && l1) ? tY[i] : pY[1][i];
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                pC[0][k] = (use && !l1) ? tC[k] : pC[0][k];
+                pC[1][k] = (use && l1) ? tC[k] : pC[1][k];
+            }
         }
+    }
+    if constexpr (PARK) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l)
+            if (parked[l]) {                                        // the lanes that wrote, and no others
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pY[l][i] = park_get(*park, PARK_PRED + 6 * l + i);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) pC[l][k] = park_get(*park, PARK_PRED + 6 * l + 4 + k);
+            }
     }
     WpPar wpp[3] = {};
     if (wp_mode != 0) {
+        // PARK: qs is the picture's slice table, and the slice index comes back with the parked record
+        if constexpr (PARK) qs += park_get(*park, PARK_Q + 2) >> 16;
         const WpRaw wr = wp_raw(qs, r0, r1);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) wpp[pl] = wp_params(wr, wp_mode, dir, pl);
@@ -893,7 +965,9 @@ DEV void pack_res(const int (&res)[4][4], s16x2 (&rp)[4][2])
 // horizontal (bypass_4x4 / bypass_8x8 transform.cc:736-778; inverse_transform_4x4 / _8x8 :986-1016
 // read those modes for inter MBs too: whatever the parser's mb_t slot holds).  The flag is
 // uniform over an MB's 16 lanes, so the cross-lane carries stay inside the caller's branch.
-DEV void luma_res_bypass(const h264r_mb& q, const Inter4Lane& L, const Inter4Res& R, int t8, s16x2 (&rp)[4][2])
+// qg: the MB's record in the batch -- its prediction modes are read from there, inside this (rare)
+// branch, and not kept in two registers across the motion compensation of every MB.
+DEV void luma_res_bypass(const h264r_mb* __restrict__ qg, const Inter4Lane& L, const Inter4Res& R, int t8, s16x2 (&rp)[4][2])
 {
     const int bx = L.bx, by = L.by;
     int d[4][4];
@@ -901,7 +975,8 @@ DEV void luma_res_bypass(const h264r_mb& q, const Inter4Lane& L, const Inter4Res
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int c = 0; c < 4; ++c) d[i][c] = level_at(R, i, c);
-    const uint32_t* qw = reinterpret_cast<const uint32_t*>(&q);
+    const uint32_t* qw = reinterpret_cast<const uint32_t*>(qg);
+    static_assert(offsetof(h264r_mb, ipred) == 20, "dwords 5 and 6 of the record");
     const uint64_t ipw = (uint64_t)qw[5] | ((uint64_t)qw[6] << 32);
     const int bk = t8 ? L.b8 : (by >> 1) * 8 + (bx >> 1) * 4 + (by & 1) * 2 + (bx & 1);
     const int mode = (int)((ipw >> (4 * bk)) & 15);
@@ -1036,16 +1111,29 @@ DEV void luma_res_8x8(const Inter4Lane& L, const Inter4Res& R, int per, int t8, 
 // Luma residual of my block (transform.cc:1058-1073): rp[i][h] = {row i's columns 2h, 2h + 1} as a
 // 16-bit pair, what the construction takes (construct4).  (Each path dequantises for itself: the
 // lossless one takes the levels, the 4x4 one a biased form its range test reads.)
-template <bool PK>
-DEV void inter4_luma_residual(const h264r_mb& q, const Inter4Lane& L, const Inter4Res& R, s16x2 (&rp)[4][2])
+// PARK (the generic stages of k_inter4r): the luma prediction predY waits in LDS while a wave with
+// T8x8 MBs runs its 8x8 transform, the widest stage after the motion compensation (Inter4Park).
+template <bool PK, bool PARK = false>
+DEV void inter4_luma_residual(const h264r_mb& q, const h264r_mb* __restrict__ qg, const Inter4Lane& L, const Inter4Res& R,
+                              s16x2 (&rp)[4][2], uint32_t (&predY)[4], Inter4Park* park = nullptr)
 {
 #pragma unroll
     for (int i = 0; i < 4; ++i) rp[i][0] = rp[i][1] = splat16(0);
     if (!__any((q.cbp & 15) != 0)) return;
     const int t8 = (q.flags & H264R_MBF_T8x8) != 0, per = q.qp_scaled[0] / 6;
-    if (q.flags & H264R_MBF_BYPASS) luma_res_bypass(q, L, R, t8, rp);
+    if (q.flags & H264R_MBF_BYPASS) luma_res_bypass(qg, L, R, t8, rp);
     else if (!__any(t8 != 0)) luma_res_4x4<PK>(R, per, t8, rp);
-    else luma_res_8x8(L, R, per, t8, rp);
+    else {
+        if constexpr (PARK) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) park_put(*park, PARK_PRED + i, predY[i]);
+        }
+        luma_res_8x8(L, R, per, t8, rp);
+        if constexpr (PARK) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) predY[i] = park_get(*park, PARK_PRED + i);
+        }
+    }
 }
 // H264R_INTER_DIAG 64 (wrong output): the luma levels loaded, not transformed (16: R is empty)
 DEV void luma_res_stub(const Inter4Res& R, s16x2 (&rp)[4][2])
@@ -1230,10 +1318,12 @@ DEV void inter4_store_chroma(uint8_t* rmb, const Inter4Lane& L, const uint32_t (
 // tag): k_inter_sp's (mb_inter_sp.h).
 // PLAIN: a wave of a plain picture (inter4_plain_picture) that passed inter4_plain_wave --
 // P and I slices in the LDS copy, default weights, list 0 alone: no SP test, no list-1 motion word,
-// and inter4_predict's one-list form.
+// and inter4_predict's one-list form; m0_plain is its list-0 motion word (the kernel's, for its records).
+// park: the workgroup's Inter4Park, which the generic instantiation needs and the PLAIN one never touches.
 template <bool PLAIN = false>
 DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int aend, int lane,
-                    const Inter4Lds& S, int* sp_flag, const Inter4Pre& pre, uint8_t* __restrict__ recon, int tag)
+                    const Inter4Lds& S, int* sp_flag, const Inter4Pre& pre, uint8_t* __restrict__ recon, int tag,
+                    Inter4Park* park = nullptr, uint2 m0_plain = make_uint2(0, 0))
 {
     constexpr int DIAG = H264R_INTER_DIAG;
     constexpr bool PK = (H264R_INTER_FAST & 1) != 0;
@@ -1241,38 +1331,66 @@ DEV void inter4_mbs(const h264r_batch& b, const Geom& g, int pic, int a0, int ae
     const h264r_slice* slices = b.slices + (size_t)pic * b.slice_stride;
     // MB record (inter4_pre: two 16-byte loads -- a struct copy becomes one byte load per field,
     // each waited on its own), its slice header and the motion of this block
-    const h264r_mb q = pre.q;
-    const uint2 qsh = slice_hdr<PLAIN>(slices, S, q.slice);
-    const uint2 m0 = motion_word<PLAIN>(pre.mv[0], pre.ri[0], slices, S, q.slice, 0);
+    const h264r_mb q0 = pre.q;
+    const uint2 qsh = slice_hdr<PLAIN>(slices, S, q0.slice);
+    // (PLAIN: the caller's list-0 motion word, which its records needed anyway; formed here again it
+    // was one with the caller's, and what both derive from it was kept across the records in scratch)
+    const uint2 m0 = PLAIN ? m0_plain : motion_word<PLAIN>(pre.mv[0], pre.ri[0], slices, S, q0.slice, 0);
     uint2 m1 = inter4_no_list();
-    if constexpr (!PLAIN) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, q.slice, 1);
+    if constexpr (!PLAIN) m1 = motion_word(pre.mv[1], pre.ri[1], slices, S, q0.slice, 1);
 
-    const bool pcm = q.mb_type == H264R_I_PCM;
-    if (!L.valid || (mb_is_intra(q) && !pcm)) return;                // intra: k_intra_* (lanes idle here)
+    const bool pcm = q0.mb_type == H264R_I_PCM;
+    if (!L.valid || (mb_is_intra(q0) && !pcm)) return;                // intra: k_intra_* (lanes idle here)
     if constexpr (!PLAIN)
-        if ((qsh.x & 255) == H264R_SLICE_SP && !mb_is_intra(q)) { *sp_flag = tag; return; }   // k_inter_sp's
-    if (pcm) { inter4_pcm(recon_mb(recon, g, pic, L.aa), L, b.levels + q.coef_off); return; }
+        if ((qsh.x & 255) == H264R_SLICE_SP && !mb_is_intra(q0)) { *sp_flag = tag; return; }   // k_inter_sp's
+    if (pcm) { inter4_pcm(recon_mb(recon, g, pic, L.aa), L, b.levels + q0.coef_off); return; }
 
     uint32_t predY[4], predC[2];
-    inter4_predict<PLAIN>(b, g, pic, L, S, &slices[q.slice], qsh.y & 255, m0, m1, predY, predC);
+    if constexpr (PLAIN) {
+        inter4_predict<true>(b, g, pic, L, S, &slices[q0.slice], qsh.y & 255, m0, m1, predY, predC);
+    } else {
+        // the generic stages: the record waits in LDS (Inter4Park) and comes back as q below
+        park_put_mb(*park, q0);
+        inter4_predict<false, true>(b, g, pic, L, S, slices, qsh.y & 255, m0, m1, predY, predC, park);
+    }
+    h264r_mb q = q0;
+    Inter4Lane Lr = L;
+    if constexpr (!PLAIN) {
+        // ... and the lane's roles are formed again from the lane (a few VALU instructions; kept, they
+        // were spilled around the motion compensation)
+        q = park_get_mb(*park);
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        Lr = inter4_lane(g, a0, aend, ln);
+        // the chroma prediction waits out the luma residual (its 8x8 transform is the widest stage)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) park_put(*park, PARK_PRED + 4 + pl, predC[pl]);
+    }
     // What only the residual and the stores read comes after the motion compensation, so that it is
-    // not live across it: the residual inputs (30 VGPRs: k_inter4r fits 128 VGPRs = 4 waves/SIMD;
+    // not live across it: the residual inputs (30 VGPRs: with them k_inter4r first fitted 128 VGPRs;
     // config 3 475 -> 493 M MB/s, profiles/r03_h_inter_ab.txt) and the two 64-bit addresses (formed
-    // before it, the kernel took 127 VGPRs instead of 125)
+    // before it, the kernel took 127 VGPRs instead of 125).  The generic stages go further to fit 96
+    // (5 waves/SIMD): what they need after the compensation comes back from LDS or is formed again.
     Inter4Res R = {};
-    if constexpr (!(DIAG & 16)) R = inter4_res_load(q, L, b.levels + q.coef_off, &b.quant[pic]);
-    uint8_t* const rmb = recon_mb(recon, g, pic, L.aa);
+    if constexpr (!(DIAG & 16)) R = inter4_res_load(q, Lr, b.levels + q.coef_off, &b.quant[pic]);
+    uint8_t* const rmb = recon_mb(recon, g, pic, Lr.aa);
 
     s16x2 rp[4][2];
     if constexpr (DIAG & (16 | 64)) luma_res_stub(R, rp);
-    else inter4_luma_residual<PK>(q, L, R, rp);
-    if constexpr (DIAG & 1) inter4_store_luma_16b(rmb, L, predY, rp);
-    else inter4_store_luma(rmb, L, predY, rp);
+    else inter4_luma_residual<PK, !PLAIN>(q, &b.mbs[(size_t)pic * g.nmb + Lr.aa], Lr, R, rp, predY, park);
+    if constexpr (DIAG & 1) inter4_store_luma_16b(rmb, Lr, predY, rp);
+    else inter4_store_luma(rmb, Lr, predY, rp);
 
+    if constexpr (!PLAIN) {
+        // ... and so does what the chroma residual reads of the record, which is still parked
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) predC[pl] = park_get(*park, PARK_PRED + 4 + pl);
+        q = park_get_mb<2>(*park);
+    }
     s16x2 rcp[2][2];
     if constexpr (DIAG & (16 | 128)) chroma_res_stub(R, rcp);
-    else inter4_chroma_residual<PK>(q, L, R, rcp);
-    inter4_store_chroma(rmb, L, predC, rcp);
+    else inter4_chroma_residual<PK>(q, Lr, R, rcp);
+    inter4_store_chroma(rmb, Lr, predC, rcp);
 }
 
 }  // namespace h264r
