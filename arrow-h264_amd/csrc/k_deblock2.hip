@@ -18,10 +18,14 @@
 //   vertical edges   lane q filters luma rows 4q .. 4q+3 as the pairs (r, r+2) and
 //                    chroma plane q/2, rows 4(q&1) .. +3 -- filter_vertical deblock.cc:488-504;
 //                    at 8 lanes lane h takes pair h of the two
-//   horizontal edges lane q filters luma columns 4q .. 4q+3 as the pairs (c, c+2) and
-//                    chroma plane q/2, columns 4(q&1) .. +3 -- filter_horizontal :506-535;
-//                    at 8 lanes lane h takes pair h and the partner lane's result comes
-//                    back by one DPP move to rebuild the dword
+//   horizontal edges lane q filters luma columns 4q .. 4q+3 and chroma plane q/2, columns
+//                    4(q&1) .. +3 -- filter_horizontal :506-535; at 8 lanes lane h takes the
+//                    adjacent columns (2h, 2h+1) of the dword and stores them itself, as the
+//                    dword's 16-bit half h, in the rows an edge can change (HALVES; the two lanes
+//                    of a dword are a two-way bank conflict in one store instruction).  At 4 lanes,
+//                    and in the form before round 11 (H264R_DB2_STEP bit 0 clear, mb_deblock2.h),
+//                    the pairs are (c, c+2), and at 8 lanes the partner lane's pair came back by
+//                    one DPP move per row to rebuild a dword that both lanes then stored
 //
 // Every operand is an s16x2 of two lines (mb_deblock2.h); the transposition between
 // the two passes is free, since both read the MB from LDS.  Each unit's MB row lives
@@ -134,11 +138,30 @@ struct alignas(16) UpLds {     // the band's first row: rows 13..15 (chroma 7) o
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));   // native vectors: registers, not stack
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 
-// {byte j, byte j + 2} of one dword as an s16x2 (the column pair (j, j+2)).
-DEV s2 unpack_cols(uint32_t w, int j) { return as_s2(__builtin_amdgcn_perm(w, w, 0x0C000C00u | ((uint32_t)(j + 2) << 16) | (uint32_t)j)); }
+// 8 lanes per unit, H264R_DB2_STEP bit 0 (mb_deblock2.h): in the horizontal pass lane (q, h) holds the
+// adjacent columns {2h, 2h+1} of its dword and stores them itself as the dword's 16-bit half h.
+constexpr bool HALVES = NH == 2 && (H264R_DB2_STEP & 1) != 0;
+// {byte j, byte j + 2} of one dword as an s16x2 (the column pair (j, j+2)); HALVES: {byte 2j, byte 2j + 1}.
+DEV s2 unpack_cols(uint32_t w, int j)
+{
+    if constexpr (HALVES) return as_s2(__builtin_amdgcn_perm(w, w, 0x0C000C00u | ((uint32_t)(2 * j + 1) << 16) | (uint32_t)(2 * j)));
+    return as_s2(__builtin_amdgcn_perm(w, w, 0x0C000C00u | ((uint32_t)(j + 2) << 16) | (uint32_t)j));
+}
+// HALVES: a lane's column pair as the two bytes of half h of the LDS dword *dw (the other half is the
+// partner lane's: one instruction, two lanes, one dword).
+typedef uint16_t __attribute__((may_alias)) u16_alias;
+DEV void store_half(uint32_t* dw, int h, s2 c)
+{
+    reinterpret_cast<u16_alias*>(dw)[h] = (uint16_t)__builtin_amdgcn_perm(as_w(c), as_w(c), 0x0C0C0200u);
+}
 // Column pairs (0, 2) and (1, 3) back into one dword.
 DEV uint32_t pack_cols(s2 c0, s2 c1) { return __builtin_amdgcn_perm(as_w(c1), as_w(c0), 0x06020400u); }
-DEV s2 bs_pair(uint32_t w, int slo, int shi) { return (s2){(short)((w >> (8 * slo)) & 255), (short)((w >> (8 * shi)) & 255)}; }
+// bytes slo and shi of a bS word for edge_params; sel = bs_selector(slo, shi), formed once per lane
+DEV s2 bs_pair(uint32_t w, int slo, int shi, uint32_t sel)
+{
+    if constexpr (DB2_BS_PERM) return bs_tagged(w, sel);
+    return (s2){(short)((w >> (8 * slo)) & 255), (short)((w >> (8 * shi)) & 255)};
+}
 
 template <int AUX = 0>
 DEV void st16(__amdgpu_buffer_rsrc_t r, uint32_t off, v4u v)
@@ -275,6 +298,12 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
     const uint32_t yrow = active ? (uint32_t)(pic - pic0) * ysz + (uint32_t)y * 16u * Wl : OOB;
     const uint32_t crow = active ? (uint32_t)(pic - pic0) * csz + (uint32_t)y * 8u * Wc : OOB;
     const int p = q >> 1, d = q & 1;                                                    // my chroma plane / dword
+    // my bS bytes of an edge's word: luma segment q twice; chroma segments 2d and 2d + 1 -- the rows
+    // (r, r + 2) of a vertical edge and the columns (c, c + 2) of a horizontal one; HALVES: the adjacent
+    // columns 4d + 2h and 4d + 2h + 1 of a horizontal edge are both in segment 2d + h
+    const int hs0 = HALVES ? 2 * d + h : 2 * d, hs1 = HALVES ? 2 * d + h : 2 * d + 1;
+    const uint32_t bsel_y = pinned(bs_selector(q, q)), bsel_c = pinned(bs_selector(2 * d, 2 * d + 1));
+    const uint32_t bsel_ch = pinned(bs_selector(hs0, hs1));
     const v4u* info_row = reinterpret_cast<const v4u*>(dbinfo + (size_t)pic * g.nmb + (size_t)yc * W);
     // byte offsets of this unit's record rows in hb, through one wave-uniform descriptor
     const uint32_t hb_bytes = (uint32_t)b.num_pics * 2u * (uint32_t)W * RECG * 8u;
@@ -467,6 +496,10 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
         }
         // edge words of my chroma plane (par[3 + 3p ..], selected without indexing by p)
         const uint32_t cpar[3] = {p ? inf[14] : inf[11], p ? inf[15] : inf[12], p ? inf[16] : inf[13]};
+        // the six edge words expanded once for the step's twelve edges (mb_deblock2.h ParP): luma /
+        // chroma {left MB edge, top MB edge, internal edges}
+        [[maybe_unused]] const ParP py[3] = {par_params(inf[8]), par_params(inf[9]), par_params(inf[10])};
+        [[maybe_unused]] const ParP pc[3] = {par_params(cpar[0]), par_params(cpar[1]), par_params(cpar[2])};
 
         // 2. vertical edges of MB x (deblock.cc:488-504)
         {
@@ -474,7 +507,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             // luma rows (4q + i, 4q + i + 2): bS of V edge e, segment q = byte 4e + q
             EdgeP ev[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ev[e] = edge_params(inf[8 + (e == 0 ? 0 : 2)], bs_pair(inf[e], q, q));
+            for (int e = 0; e < 4; ++e) ev[e] = edge_params<false>(py[e == 0 ? 0 : 2], bs_pair(inf[e], q, q, bsel_y));
 #pragma unroll
             for (int ii = 0; ii < 2 / NH; ++ii) {
                 const int i = NH == 2 ? h : ii;
@@ -507,7 +540,8 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             // spilled at three waves per SIMD)
             load_record(x);
             // chroma plane p rows (4d + i, +2); chroma edge 0 = luma edge 0, edge 1 (col 4) =
-            // luma edge 2; row j takes the bS of luma row 2j: segment j / 2 (deblock.cc:430-433, 460)
+            // luma edge 2; row j takes the bS of luma row 2j: segment j / 2 (deblock.cc:430-433, 460),
+            // for the rows 4d + i and 4d + i + 2, i < 2, segments 2d and 2d + 1 (bsel_c)
           if constexpr (DOC) {
 #pragma unroll
             for (int ii = 0; ii < 2 / NH; ++ii) {
@@ -516,7 +550,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
                 EdgeP ec[2];
 #pragma unroll
                 for (int e = 0; e < 2; ++e)
-                    ec[e] = edge_params(cpar[e == 0 ? 0 : 2], bs_pair(inf[2 * e], ra >> 1, rb2 >> 1));
+                    ec[e] = edge_params<true>(pc[e == 0 ? 0 : 2], bs_pair(inf[2 * e], ra >> 1, rb2 >> 1, bsel_c));
                 uint32_t la = U.c[p][ra][2 * sl + 1], lb = U.c[p][rb2][2 * sl + 1];
                 const v2u Av = *reinterpret_cast<const v2u*>(&U.c[p][ra][2 * sc]);
                 const v2u Bv = *reinterpret_cast<const v2u*>(&U.c[p][rb2][2 * sc]);
@@ -603,6 +637,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
 
         // 6. horizontal edges of MB x (deblock.cc:506-535); rows -4..-1 from the record
         uint32_t wy[20], wcv[10];
+        [[maybe_unused]] s2 hy[3], hc;           // HALVES: this lane's pairs of rows -3..-1 (chroma -1)
         {
         if constexpr (DOY) {
 #pragma unroll
@@ -611,7 +646,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             for (int r = 0; r < 16; ++r) wy[4 + r] = U.y[r][4 * sc + q];
             EdgeP eh[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) eh[e] = edge_params(inf[8 + (e == 0 ? 1 : 2)], bs_pair(inf[4 + e], q, q));
+            for (int e = 0; e < 4; ++e) eh[e] = edge_params<false>(py[e == 0 ? 1 : 2], bs_pair(inf[4 + e], q, q, bsel_y));
             s2 c[2 / NH][20];
 #pragma unroll
             for (int jj = 0; jj < 2 / NH; ++jj) {
@@ -624,6 +659,14 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
                     filter2<false, false>(c[jj][4 * e], c[jj][4 * e + 1], c[jj][4 * e + 2], c[jj][4 * e + 3], c[jj][4 * e + 4],
                                           c[jj][4 * e + 5], c[jj][4 * e + 6], c[jj][4 * e + 7], eh[e]);
             }
+            if constexpr (HALVES) {
+                // each lane stores its own half of every row an edge can change: rows 14 and 15 are
+                // past the reach of the last internal edge (p1..q1 = rows 10..13) and keep their bytes
+#pragma unroll
+                for (int r = 1; r < 4; ++r) hy[r - 1] = c[0][r];
+#pragma unroll
+                for (int r = 0; r < 14; ++r) store_half(&U.y[r][4 * sc + q], h, c[0][4 + r]);
+            } else {
 #pragma unroll
             for (int r = 1; r < 20; ++r) {
                 if constexpr (NH == 1) {
@@ -635,17 +678,18 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) U.y[r][4 * sc + q] = wy[4 + r];
+            }
         }
         if constexpr (DOC) {
             // chroma plane p, columns 4d .. 4d+3 (dword d), rows -2..7; the halves of a pair sit
-            // in segments 2d and 2d+1 of luma H edge 0 / 2
+            // in segments 2d and 2d+1 of luma H edge 0 / 2 (HALVES: both in segment 2d+h)
 #pragma unroll
             for (int r = 0; r < 2; ++r) wcv[r] = (uint32_t)rin[4 + r];
 #pragma unroll
             for (int r = 0; r < 8; ++r) wcv[2 + r] = U.c[p][r][2 * sc + d];
             EdgeP eh[2];
 #pragma unroll
-            for (int e = 0; e < 2; ++e) eh[e] = edge_params(cpar[e == 0 ? 1 : 2], bs_pair(inf[4 + 2 * e], 2 * d, 2 * d + 1));
+            for (int e = 0; e < 2; ++e) eh[e] = edge_params<true>(pc[e == 0 ? 1 : 2], bs_pair(inf[4 + 2 * e], hs0, hs1, bsel_ch));
             s2 c[2 / NH][10];
 #pragma unroll
             for (int jj = 0; jj < 2 / NH; ++jj) {
@@ -656,6 +700,13 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
                 filter2<true, true>(d0, d0, c[jj][0], c[jj][1], c[jj][2], c[jj][3], d1, d1, eh[0]);
                 filter2<false, true>(d0, d0, c[jj][4], c[jj][5], c[jj][6], c[jj][7], d1, d1, eh[1]);
             }
+            if constexpr (HALVES) {
+                // a chroma edge changes p0 and q0 only: rows -1 and 0, rows 3 and 4
+                hc = c[0][1];
+                store_half(&U.c[p][0][2 * sc + d], h, c[0][2]);
+                store_half(&U.c[p][3][2 * sc + d], h, c[0][5]);
+                store_half(&U.c[p][4][2 * sc + d], h, c[0][6]);
+            } else {
 #pragma unroll
             for (int r = 1; r < 10; ++r) {
                 if constexpr (NH == 1) {
@@ -667,6 +718,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             }
 #pragma unroll
             for (int r = 0; r < 8; ++r) U.c[p][r][2 * sc + d] = wcv[2 + r];
+            }
         }
         }
 
@@ -688,9 +740,16 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(H
             if constexpr (DOY) {
                 uint32_t* yd = rb ? &TA.y[13][x % SG][q] : &TU.yu[0][x % SG][q];
 #pragma unroll
-                for (int r = 1; r < 4; ++r) yd[(r - 1) * 4 * SG] = wy[r];
+                for (int r = 1; r < 4; ++r) {
+                    if constexpr (HALVES) store_half(&yd[(r - 1) * 4 * SG], h, hy[r - 1]);
+                    else yd[(r - 1) * 4 * SG] = wy[r];
+                }
             }
-            if constexpr (DOC) *(rb ? &TA.c[p][7][x % SG][d] : &TU.cu[p][x % SG][d]) = wcv[1];
+            if constexpr (DOC) {
+                uint32_t* cd = rb ? &TA.c[p][7][x % SG][d] : &TU.cu[p][x % SG][d];
+                if constexpr (HALVES) store_half(cd, h, hc);
+                else *cd = wcv[1];
+            }
         }
         // 8. what the next step fills: MB x+2 and its DbInfo
         fetch(x + 2);

@@ -62,29 +62,118 @@ DEV void merge2(s2 c0, s2 c1, int half, uint32_t& lo, uint32_t& hi)
     hi = __builtin_amdgcn_perm(hi, u, half ? 0x03020504u : 0x07060302u);
 }
 
+// The step's form (A/B knob; 0 is the form before round 11, kept compilable):
+//   bit 0  k_deblock2.hip, 8 lanes per unit: the horizontal pass filters adjacent column pairs and each
+//          lane stores its own 16-bit half of a dword (no partner move, no merge, no select)
+//   bit 1  an edge word is expanded once per step (ParP), an edge adds only its bS permute
+//   bit 2  the constants a filter2 instance formed from its edge (bS - 1, tc0 + 1 / + 2, -tc0,
+//          (alpha >> 2) + 1) come with the EdgeP
+//   bit 3  an edge's two bS bytes leave the DbInfo word by one permute whose selector the lane keeps,
+//          already in the form the tc0 permute takes (bs_tagged): no shift, mask, splat and or per edge
+// Bits 0 and 3 are on.  Bits 1 and 2 remove no instruction at 8 lanes per unit (the compiler merges the
+// expansions of one word itself; an edge has one filter2 instance per lane) and measured +1.4 % and +0.3 %
+// of k_deblock2 alone (profiles/r11_a_deblock_step_ab.txt).
+#ifndef H264R_DB2_STEP
+#define H264R_DB2_STEP 9
+#endif
+constexpr bool DB2_PAR_ONCE = (H264R_DB2_STEP & 2) != 0, DB2_EDGE_CONST = (H264R_DB2_STEP & 4) != 0;
+constexpr bool DB2_BS_PERM = (H264R_DB2_STEP & 8) != 0;
+
+// A value the compiler must keep in its register rather than form again where it is used.
+DEV uint32_t pinned(uint32_t w)
+{
+    asm("" : "+v"(w));
+    return w;
+}
+DEV s2 pinned(s2 v) { return as_s2(pinned(as_w(v))); }
+
 // Per-edge parameters of the two halves: alpha / beta of the edge, bS and tc0 per half.
 struct EdgeP {
     s2 am1, bm1;        // alpha - 1, beta - 1
     s2 bs;              // bS per half
     s2 tc0;             // tc0(bS) per half (0 for bS 0 and 4)
     s2 alpha;
+    // DB2_EDGE_CONST
+    s2 bsm1;            // bS - 1
+    s2 tcb;             // tc0 + 1 (chroma) / tc0 + 2 (luma): tc before the ap / aq terms
+    s2 ntc0;            // -tc0
+    s2 a4;              // (alpha >> 2) + 1
 };
 
 // par = edge_word() (mb_deblock.h): alpha | beta << 8 | tc0(bS 1..3) << 16 / 21 / 26.
-// bs2 = {bS of half a, bS of half b}.
-DEV EdgeP edge_params(uint32_t par, s2 bs2)
+// The bytes {0, tc0(1), tc0(2), tc0(3)} that a half's bS indexes.
+DEV uint32_t tc0_table(uint32_t par) { return (((par >> 16) & 31) << 8) | (((par >> 21) & 31) << 16) | (((par >> 26) & 31) << 24); }
+
+// What an edge word gives every edge that uses it, formed once per step (DB2_PAR_ONCE; otherwise the
+// word itself, expanded by each edge_params as before).
+struct ParP {
+    uint32_t par;
+    s2 alpha, am1, bm1, a4;
+    uint32_t T;
+};
+DEV ParP par_params(uint32_t par)
+{
+    ParP pp;
+    pp.par = par;
+    if constexpr (DB2_PAR_ONCE) {
+        const short alpha = (short)(par & 255), beta = (short)((par >> 8) & 255);
+        pp.alpha = pinned(sp2(alpha));
+        pp.am1 = pinned(sp2((short)(alpha - 1)));
+        pp.bm1 = pinned(sp2((short)(beta - 1)));
+        pp.a4 = pinned(sp2((short)((alpha >> 2) + 1)));
+        pp.T = pinned(tc0_table(par));
+    }
+    return pp;
+}
+
+// DB2_BS_PERM: bytes slo and shi of a DbInfo bS word as {bS | 0x0c00} per half, which is the selector of
+// the tc0 permute as it stands (selector byte 0x0c gives 0).  bs_selector is per lane, not per edge.
+constexpr short BS_TAG = 0x0c00;
+DEV uint32_t bs_selector(int slo, int shi) { return 0x04000400u | (uint32_t)shi << 16 | (uint32_t)slo; }
+DEV s2 bs_tagged(uint32_t w, uint32_t selector)
+{
+    // perm selectors: 0..3 = bytes of the second operand (w), 4 = byte 0 of the first
+    return as_s2(__builtin_amdgcn_perm(0x0c0c0c0cu, w, selector));
+}
+
+// bs2 = {bS of half a, bS of half b} (DB2_BS_PERM: bs_tagged).  CHROMA: the edge of a chroma filter2
+// instance (tcb).
+template <bool CHROMA>
+DEV EdgeP edge_params(const ParP& pp, s2 bs2)
 {
     EdgeP e;
-    const short alpha = (short)(par & 255), beta = (short)((par >> 8) & 255);
-    e.alpha = sp2(alpha);
-    e.am1 = sp2((short)(alpha - 1));
-    e.bm1 = sp2((short)(beta - 1));
-    e.bs = bs2;
+    uint32_t T;
+    if constexpr (DB2_PAR_ONCE) {
+        e.alpha = pp.alpha; e.am1 = pp.am1; e.bm1 = pp.bm1; e.a4 = pp.a4;
+        T = pp.T;
+    } else {
+        const short alpha = (short)(pp.par & 255), beta = (short)((pp.par >> 8) & 255);
+        e.alpha = sp2(alpha);
+        e.am1 = sp2((short)(alpha - 1));
+        e.bm1 = sp2((short)(beta - 1));
+        e.a4 = (e.alpha >> sp2(2)) + sp2(1);
+        T = tc0_table(pp.par);
+    }
     // tc0(bS) of each half by one byte permute: bS (0..4, the half's low byte) indexes the
     // bytes {0, tc0(1), tc0(2), tc0(3)} and, for bS 4, byte 0 of a zero operand
-    const uint32_t T = (((par >> 16) & 31) << 8) | (((par >> 21) & 31) << 16) | (((par >> 26) & 31) << 24);
-    e.tc0 = as_s2(__builtin_amdgcn_perm(0u, T, as_w(bs2) | 0x0c000c00u));
+    if constexpr (DB2_BS_PERM) {
+        e.bs = bs2 - sp2(BS_TAG);       // folds into the constants bS is compared with
+        e.tc0 = as_s2(__builtin_amdgcn_perm(0u, T, as_w(bs2)));
+    } else {
+        e.bs = bs2;
+        e.tc0 = as_s2(__builtin_amdgcn_perm(0u, T, as_w(bs2) | 0x0c000c00u));
+    }
+    e.bsm1 = e.bs - sp2(1);
+    e.tcb = e.tc0 + sp2(CHROMA ? 1 : 2);
+    e.ntc0 = -e.tc0;
     return e;
+}
+
+// -1 where bS >= 4 (bS is 0..4)
+DEV s2 bs4_mask(s2 bs)
+{
+    if constexpr (DB2_BS_PERM) return opaque_mask(neg_mask(sp2(3) - bs));
+    return opaque_mask(neg_mask(bs - sp2(4)) ^ sp2(-1));
 }
 
 // filterSamplesFlag and friends for luma (chroma = false) or chroma lines;
@@ -94,15 +183,15 @@ DEV void filter2(s2& p3, s2& p2, s2& p1, s2& p0, s2& q0, s2& q1, s2& q2, s2& q3,
 {
     const s2 dpq = absd(p0, q0);
     // -1 where NOT (bS != 0 && |p0-q0| < alpha && |p1-p0| < beta && |q1-q0| < beta)
-    const s2 nf = neg_mask(smin(smin(e.am1 - dpq, e.bm1 - absd(p1, p0)), smin(e.bm1 - absd(q1, q0), e.bs - sp2(1))));
+    const s2 nf = neg_mask(smin(smin(e.am1 - dpq, e.bm1 - absd(p1, p0)), smin(e.bm1 - absd(q1, q0), DB2_EDGE_CONST ? e.bsm1 : e.bs - sp2(1))));
     if (CHROMA) {
         // filter_normal, chromaStyleFilteringFlag: tc = tc0 + 1, p0 / q0 only (deblock.cc:380-400)
-        const s2 tc = e.tc0 + sp2(1);
+        const s2 tc = DB2_EDGE_CONST ? e.tcb : e.tc0 + sp2(1);
         s2 d = ((q0 - p0) * sp2(4) + (p1 - q1) + sp2(4)) >> sp2(3);
         d = smin(smax(d, -tc), tc);
         s2 np0 = clamp255(p0 + d), nq0 = clamp255(q0 - d);
         if (STRONG) {                                  // filter_strong, chroma (deblock.cc:350-364)
-            const s2 is4 = opaque_mask(neg_mask(e.bs - sp2(4)) ^ sp2(-1));          // -1 where bS >= 4
+            const s2 is4 = bs4_mask(e.bs);          // -1 where bS >= 4
             np0 = sel(is4, (p1 * sp2(2) + p0 + q1 + sp2(2)) >> sp2(2), np0);
             nq0 = sel(is4, (q1 * sp2(2) + q0 + p1 + sp2(2)) >> sp2(2), nq0);
         }
@@ -113,17 +202,18 @@ DEV void filter2(s2& p3, s2& p2, s2& p1, s2& p0, s2& q0, s2& q1, s2& q2, s2& q3,
     const s2 nap = neg_mask(e.bm1 - absd(p2, p0));         // -1 where NOT (|p2-p0| < beta)
     const s2 naq = neg_mask(e.bm1 - absd(q2, q0));
     // filter_normal (deblock.cc:372-415)
-    const s2 tc = e.tc0 + sp2(2) + nap + naq;               // tc0 + (ap < beta) + (aq < beta)
+    const s2 tc = (DB2_EDGE_CONST ? e.tcb : e.tc0 + sp2(2)) + nap + naq;               // tc0 + (ap < beta) + (aq < beta)
     s2 d = ((q0 - p0) * sp2(4) + (p1 - q1) + sp2(4)) >> sp2(3);
     d = smin(smax(d, -tc), tc);
     s2 np0 = clamp255(p0 + d), nq0 = clamp255(q0 - d);
     const s2 avg = (p0 + q0 + sp2(1)) >> sp2(1);
-    s2 np1 = sel(nap, p1, p1 + smin(smax((p2 + avg - p1 * sp2(2)) >> sp2(1), -e.tc0), e.tc0));
-    s2 nq1 = sel(naq, q1, q1 + smin(smax((q2 + avg - q1 * sp2(2)) >> sp2(1), -e.tc0), e.tc0));
+    const s2 ntc0 = DB2_EDGE_CONST ? e.ntc0 : -e.tc0;
+    s2 np1 = sel(nap, p1, p1 + smin(smax((p2 + avg - p1 * sp2(2)) >> sp2(1), ntc0), e.tc0));
+    s2 nq1 = sel(naq, q1, q1 + smin(smax((q2 + avg - q1 * sp2(2)) >> sp2(1), ntc0), e.tc0));
     s2 np2 = p2, nq2 = q2;
     if (STRONG) {                                          // filter_strong (deblock.cc:327-370)
-        const s2 is4 = opaque_mask(neg_mask(e.bs - sp2(4)) ^ sp2(-1));
-        const s2 nstrong = neg_mask(((e.alpha >> sp2(2)) + sp2(1)) - dpq);   // NOT (|p0-q0| < (alpha >> 2) + 2)
+        const s2 is4 = bs4_mask(e.bs);
+        const s2 nstrong = neg_mask((DB2_EDGE_CONST ? e.a4 : (e.alpha >> sp2(2)) + sp2(1)) - dpq);   // NOT (|p0-q0| < (alpha >> 2) + 2)
         const s2 nsp = nap | nstrong, nsq = naq | nstrong;
         const s2 s_p0 = sel(nsp, (p1 * sp2(2) + p0 + q1 + sp2(2)) >> sp2(2),
                             (p2 + p1 * sp2(2) + p0 * sp2(2) + q0 * sp2(2) + q1 + sp2(4)) >> sp2(3));
