@@ -319,14 +319,16 @@ static int recon_launches(h264r_ctx* c, const Stage& S, hipStream_t s, int2 rows
     const SyncWords SW{P, H};
     uint8_t* recon = S.recon;
     const int groups = (W * HB + 15) / 16;
-    // groups per workgroup (launch_cfg.h), 8 XCD bands (k_recon.hip inter4_groups)
-    const dim3 igrid(8 * ((groups + 8 * H264R_INTER_GROUPS - 1) / (8 * H264R_INTER_GROUPS)), P);
+    // 8 XCD bands of 16-MB units, each unit 4 / H264R_INTER_WG_WAVES groups of a workgroup's MBs,
+    // H264R_INTER_GROUPS groups per workgroup (launch_cfg.h; k_recon.hip inter4_groups)
+    const int band_groups = ((groups + 7) / 8) * (4 / H264R_INTER_WG_WAVES);
+    const dim3 igrid(8 * ((band_groups + H264R_INTER_GROUPS - 1) / H264R_INTER_GROUPS), P);
     {
         Timed t(c, 0, s);
         // the deblocking records and the inter / I_PCM reconstruction in one launch, which also
         // zeroes the stage's sync words and the level counters
         if (++X.tag <= 0) X.tag = 1;
-        hipLaunchKernelGGL(k_inter4r, igrid, dim3(256), 0, s, b, S.dbinfo, rows, S.sp_flag, recon, X.tag, sync,
+        hipLaunchKernelGGL(k_inter4r, igrid, dim3(64 * H264R_INTER_WG_WAVES), 0, s, b, S.dbinfo, rows, S.sp_flag, recon, X.tag, sync,
                            (int)SW.zeroed(), levels ? X.d_lcnt.p : nullptr, levels ? 3 * LEVEL_IDS : 0);
         HIP_OK(hipGetLastError());
         // inter MBs of SP slices (a short launch when the batch has none)

@@ -27,9 +27,9 @@ struct LdsRegs {
     const uint8_t* plane;
     uint2 refs, hdr;
 };
-DEV LdsRegs inter4_lds_load(const h264r_batch& b, int pic)
+// t: the entry (0 .. 255) this thread copies -- threadIdx.x in a 256-thread workgroup
+DEV LdsRegs inter4_lds_load(const h264r_batch& b, int pic, int t)
 {
-    const int t = threadIdx.x;
     const int nsl = min(b.slice_stride, INTER4_LDS_SLICES);
     const h264r_slice* sl = b.slices + (size_t)pic * b.slice_stride;
     LdsRegs r;
@@ -40,9 +40,8 @@ DEV LdsRegs inter4_lds_load(const h264r_batch& b, int pic)
     r.hdr = *reinterpret_cast<const uint2*>(&sl[min(t, nsl - 1)]);
     return r;
 }
-DEV void inter4_lds_store(const h264r_batch& b, const LdsRegs& r, Inter4Lds& S)
+DEV void inter4_lds_store(const h264r_batch& b, const LdsRegs& r, Inter4Lds& S, int t)
 {
-    const int t = threadIdx.x;
     const int nsl = min(b.slice_stride, INTER4_LDS_SLICES);
     if (t < 3 * H264R_MAX_SLOTS) S.planes[t] = r.plane;
     if (t < nsl * 4) *reinterpret_cast<uint2*>(&S.ref_slot[t >> 2][0][0] + 8 * (t & 3)) = r.refs;
@@ -51,22 +50,29 @@ DEV void inter4_lds_store(const h264r_batch& b, const LdsRegs& r, Inter4Lds& S)
         S.slice_type[t] = (uint8_t)(r.hdr.x & 255);
     }
 }
-DEV void inter4_lds(const h264r_batch& b, int pic, Inter4Lds& S) { inter4_lds_store(b, inter4_lds_load(b, pic), S); }
+DEV void inter4_lds(const h264r_batch& b, int pic, Inter4Lds& S)
+{
+    inter4_lds_store(b, inter4_lds_load(b, pic, threadIdx.x), S, threadIdx.x);
+}
 
-// The 16-MB groups [grp, gend) of one k_inter4r workgroup: XCD-aware (below),
-// `per` (H264R_INTER_GROUPS, launch_cfg.h) consecutive groups of its
-// XCD's band per workgroup, so that the workgroup's LDS tables are filled once for several
-// groups.
+// The groups [grp, gend) of one k_inter4r workgroup: XCD-aware (below), `per` (H264R_INTER_GROUPS,
+// launch_cfg.h) consecutive groups of its XCD's band per workgroup, so that the workgroup's LDS
+// tables are filled once for several groups.  A group is the INTER4_MBS MBs the workgroup's waves
+// take together: 8 at H264R_INTER_WG_WAVES 2, 16 at 4.  The bands are cut in 16-MB units either
+// way, so a unit is 16 / INTER4_MBS consecutive workgroups of one band and the bands do not move
+// with the workgroup size.
 DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 {
-    const int groups = (g.wmb * (rows.y - rows.x) + 15) / 16, gb = (groups + 7) / 8;
+    constexpr int SUB = 16 / INTER4_MBS;                   // groups per 16-MB unit
+    const int mbs = g.wmb * (rows.y - rows.x);
+    const int groups = (mbs + INTER4_MBS - 1) / INTER4_MBS, gb = (((mbs + 15) / 16 + 7) / 8) * SUB;
     const int band = blockIdx.x & 7;
     grp = band * gb + (blockIdx.x >> 3) * per;
     gend = min(min(grp + per, (band + 1) * gb), groups);
     return grp < gend;
 }
 
-// k_inter4r: per 16-MB group of a workgroup, first the deblocking records DbInfo of the group's
+// k_inter4r: per group of a workgroup (inter4_groups), first the deblocking records DbInfo of the group's
 // MBs (dbinfo_block: their neighbour records and motion are loaded with the group's own record and
 // motion), then the reconstruction of its inter and I_PCM MBs (inter4_mbs); the records' registers
 // are dead before the motion compensation starts (96 VGPRs with both instantiations below, 5 waves/SIMD).  Round 6 folded the
@@ -79,8 +85,8 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // sp_flag: set to the launch tag when an inter MB of an SP slice was met (k_inter_sp then runs; a
 // tag, not a flag, so nothing has to zero it between launch sequences -- the word is the host's
 // own array of SP tags, outside the sync region this kernel zeroes, and only ever holds tags).
-// Grid (8 * ceil(groups / (8 * per)), pictures), XCD-aware: workgroups go round-robin to the 8
-// XCDs in launch order, so blockIdx.x % 8 is the XCD and it takes the 16-MB groups of band
+// Grid (8 * ceil(groups of a band / per), pictures), XCD-aware: workgroups go round-robin to the 8
+// XCDs in launch order, so blockIdx.x % 8 is the XCD and it takes the groups of band
 // blockIdx.x % 8 (one eighth of the MB rows) of every picture: an XCD's motion
 // compensation reads only its band of the reference pictures (+ the MV reach), which its
 // 4 MB L2 holds, instead of every XCD streaming whole references through its L2.
@@ -94,13 +100,17 @@ DEV bool inter4_groups(const Geom& g, int2 rows, int per, int& grp, int& gend)
 // and its two sides hold their registers apart (90 VGPRs the generic side alone, 93 the plain one, 96
 // the kernel, which also keeps 9 SGPRs in the lanes of a VGPR: profiles/r10_a_inter_waves5_isa.txt).
 // Both sides run at 5 waves/SIMD: the generic one parks each list's prediction, list 1's motion word
-// and the MB record in per-lane LDS slots (P below; 18 KiB of the 32 KiB a workgroup may take at 5
-// workgroups per CU) and forms the lane's roles again after the motion compensation; a plain wave
+// and the MB record in per-lane LDS slots (P below; 18 dwords per lane) and forms the lane's roles
+// again after the motion compensation; a plain wave
 // executes no parking instruction.  Config 3 kernel_ms.inter 6.24 -> 5.96 ms, configs 4 / 5 2.91 ->
 // 2.79 / 2.80 ms (profiles/r10_a_inter_waves5_ab.txt).  (The plain side as a kernel of its own,
 // k_inter4p, was the first to reach 5 waves but paid the dispatch of its workgroups for the other
 // kernel's pictures: profiles/r09_a_inter_plain_ab.txt)
-extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h264r_batch b, DbInfo* dbinfo, int2 rows,
+// Workgroups of two waves (H264R_INTER_WG_WAVES, launch_cfg.h): a workgroup's wave slots are released
+// together, and with four waves 4.61 of the 5 slots per SIMD were held on average; two-wave workgroups
+// (13,040 B of LDS, 10 per CU) took config 3's kernel_ms.inter down by 0.7 .. 1.5 %
+// (profiles/r12_a_inter_mc_wg_ab.txt).  The LDS tables are filled in 256 / threads passes.
+extern "C" __global__ __launch_bounds__(INTER4_WG_THREADS, H264R_INTER_WAVES) void k_inter4r(h264r_batch b, DbInfo* dbinfo, int2 rows,
                                                                                int* sp_flag, uint8_t* recon, int tag,
                                                                                int* zero, int nz, int* zero2, int nz2)
 {
@@ -120,15 +130,21 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int aend = rows.y * g.wmb;
     const h264r_slice* slices = b.slices + (size_t)pic * b.slice_stride;
-    int a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;
+    int a0 = rows.x * g.wmb + (grp * INTER4_WG_WAVES + wave) * 4;
+    // the LDS tables have up to 256 entries (the ref tables of 64 slices; the deblocking tables' 52 and
+    // the 96 planes fit the first pass of either workgroup size): 256 / INTER4_WG_THREADS passes
+    constexpr int FILLS = 256 / INTER4_WG_THREADS;
     const uint2 tv = db_tables_load(threadIdx.x);
     Inter4Pre pre = inter4_pre(b, g, pic, a0, aend, lane);
     DbNb nb = dbinfo_pre(b, g, pic, a0, aend, lane);
-    const LdsRegs lr = inter4_lds_load(b, pic);
+    LdsRegs lr[FILLS];
+#pragma unroll
+    for (int f = 0; f < FILLS; ++f) lr[f] = inter4_lds_load(b, pic, threadIdx.x + f * INTER4_WG_THREADS);
     const int ns = (int)ld_const(&b.pics[pic].num_slices);
     db_tables_store(T, threadIdx.x, tv);
-    inter4_lds_store(b, lr, S);
-    inter4_plain_mark(S, threadIdx.x, lr.hdr, ns);
+#pragma unroll
+    for (int f = 0; f < FILLS; ++f) inter4_lds_store(b, lr[f], S, threadIdx.x + f * INTER4_WG_THREADS);
+    inter4_plain_mark(S, threadIdx.x, lr[0].hdr, ns);
     __syncthreads();
     const bool plain = inter4_plain_picture(b, S, ns);
     for (;;) {
@@ -165,7 +181,7 @@ extern "C" __global__ __launch_bounds__(256, H264R_INTER_WAVES) void k_inter4r(h
             inter4_mbs(b, g, pic, a0, aend, ln, S, sp_flag, pre, recon, tag, &P);
         }
         if (++grp >= gend) return;
-        a0 = rows.x * g.wmb + (grp * 4 + wave) * 4;
+        a0 = rows.x * g.wmb + (grp * INTER4_WG_WAVES + wave) * 4;
         int ln2 = lane;
         asm volatile("" : "+v"(ln2));
         pre = inter4_pre(b, g, pic, a0, aend, ln2);

@@ -34,6 +34,7 @@
 // inter4_sp_mbs (mb_inter_sp.h), on the same lane roles, prediction and residual inputs.
 #pragma once
 #include "mb_deblock.h"
+#include "launch_cfg.h"
 
 // H264R_INTER_DIAG: diagnostic builds only (wrong output; make EXTRA=-DH264R_INTER_DIAG=<bits>) that
 // take one part of k_inter4r away to time the rest: 1 one 16-byte store per lane, 2 no luma
@@ -49,10 +50,19 @@
 #ifndef H264R_INTER_FAST
 #define H264R_INTER_FAST 3
 #endif
+// H264R_INTER_MC: two shorter forms around the motion compensation, each with the form before it as the other
+// side of an `if constexpr`, so that either builds from one tree for an A/B (make EXTRA=-DH264R_INTER_MC=<bits>):
+// 1 the luma and chroma window fetches clamp rows and columns by one v_med3_i32 (clip0), 2 inter4_lane divides
+// in 24 bits.  What else was tried in luma_block_pred and why it is not here: profiles/r12_a_inter_mc_wg_ab.txt.
+#ifndef H264R_INTER_MC
+#define H264R_INTER_MC 3
+#endif
 
 namespace h264r {
 
-constexpr int INTER4_MBS = 16;   // MBs per 256-thread workgroup (4 waves x 4)
+constexpr int INTER4_WG_WAVES = H264R_INTER_WG_WAVES;   // waves of a k_inter4r workgroup (launch_cfg.h)
+constexpr int INTER4_WG_THREADS = 64 * INTER4_WG_WAVES;
+constexpr int INTER4_MBS = 4 * INTER4_WG_WAVES;          // MBs per k_inter4r workgroup (4 per wave)
 constexpr int INTER4_LDS_SLICES = 64;   // slices whose ref tables the workgroup keeps in LDS
 constexpr int INTER4_PLAIN_SLICES = 8;  // slices of a plain picture at most (inter4_plain_picture)
 static_assert(INTER4_PLAIN_SLICES <= INTER4_LDS_SLICES, "a plain picture's slices are all in the LDS copy");
@@ -77,7 +87,7 @@ constexpr int PARK_M1 = 12;      // 2: list 1's motion word while list 0 is comp
 constexpr int PARK_Q = 14;       // 4: the MB record's dwords 0, 3, 2, 4 (park_put_mb)
 constexpr int INTER4_PARK_SLOTS = 18;
 struct Inter4Park {
-    uint32_t w[INTER4_PARK_SLOTS][256];
+    uint32_t w[INTER4_PARK_SLOTS][INTER4_WG_THREADS];
 };
 // (address space 3 by name: a volatile access through a generic pointer stays a flat one, 64-bit address and all)
 typedef __attribute__((address_space(3))) volatile uint32_t lds_vdword;
@@ -124,7 +134,14 @@ DEV Inter4Lane inter4_lane(const Geom& g, int a0, int aend, int lane)
     L.blk = blk; L.bx = bx; L.by = by;
     L.valid = a < aend;
     L.aa = L.valid ? a : aend - 1;
-    L.mbx = L.aa % g.wmb; L.mby = L.aa / g.wmb;
+    if constexpr (H264R_INTER_MC & 2) {
+        // an MB address is below 2^24 and a picture's width in MBs below 2^16 (level 6.2 allows 139,264 MBs):
+        // said to the compiler, the division is its 24-bit form, a third of the signed 32-bit one's instructions
+        const uint32_t ua = (uint32_t)L.aa & 0xFFFFFFu, uw = (uint32_t)g.wmb & 0xFFFFu;
+        L.mby = (int)(ua / uw); L.mbx = (int)(ua - (uint32_t)L.mby * uw);
+    } else {
+        L.mbx = L.aa % g.wmb; L.mby = L.aa / g.wmb;
+    }
     L.X4 = L.mbx * 4 + bx; L.Y4 = L.mby * 4 + by;
     L.b8 = L.cb = (by >> 1) * 2 + (bx >> 1);
     L.cr = (by & 1) * 2; L.cc = (bx & 1) * 2;
@@ -309,6 +326,16 @@ DEV s16x2 pair_at(uint32_t r0, uint32_t r1, uint32_t r2)
     return as_s16x2(K < 4 ? __builtin_amdgcn_perm(r1, r0, sel) : __builtin_amdgcn_perm(r2, r1, sel));
 }
 
+// clip3(0, hi, x) for a wave-uniform hi >= 0 as one v_med3_i32 (H264R_INTER_MC bit 0).  clip3's
+// ternaries compile to a minimum, a compare and a select: the compiler may not assume 0 <= hi.
+DEV int clip0(int hi, int x)
+{
+    if constexpr (!(H264R_INTER_MC & 1)) return clip3(0, hi, x);
+    int r;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
+    return r;
+}
+
 // The 16 luma prediction samples of one 4x4 block at integer position (x, y) and
 // quarter phase (xf, yf): spec 8.4.2.2.1 / reference get_block_luma
 // (inter_prediction.cc:158-340).  The 9 window rows y-2..y+6 are loaded at once and
@@ -322,9 +349,10 @@ DEV s16x2 pair_at(uint32_t r0, uint32_t r1, uint32_t r2)
 // per row from clip(x - 2) & ~3, row index clamped).
 DEV void luma_window_global(const uint8_t* __restrict__ img, int W, int pitch, int H, int x, int y, uint32_t (&w)[9][3])
 {
+    const int a = clip0(W - 1, x - 2) & ~3;             // (row_dwords, device_common.h, with clip0)
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
-        const gdword* q = row_dwords(img, W, pitch, H, x, y - 2 + r);
+        const gdword* q = as_global(img + (size_t)clip0(H - 1, y - 2 + r) * pitch + a);
         w[r][0] = q[0]; w[r][1] = q[1]; w[r][2] = q[2];
     }
 }
@@ -439,7 +467,7 @@ DEV u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
 DEV void chroma_block_pred2(const uint8_t* __restrict__ cb, const uint8_t* __restrict__ cr, int W, int pitch, int H, int xi,
                             int yi, int xf, int yf, uint32_t (&out)[2])
 {
-    const int a = clip3(0, W - 1, xi) & ~3;
+    const int a = clip0(W - 1, xi) & ~3;
     // both planes' three rows first (12 dwords in flight): a lane-divergent interior / edge
     // split made every row's load wait for the previous row's use, and one plane at a time
     // left the second plane's last row behind a full vmcnt wait
@@ -448,7 +476,7 @@ DEV void chroma_block_pred2(const uint8_t* __restrict__ cb, const uint8_t* __res
     for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const gdword* q = as_global((pl ? cr : cb) + (size_t)clip3(0, H - 1, yi + k) * pitch + a);
+            const gdword* q = as_global((pl ? cr : cb) + (size_t)clip0(H - 1, yi + k) * pitch + a);
             w[pl][k][0] = q[0];
             w[pl][k][1] = q[1];
         }
@@ -456,7 +484,7 @@ DEV void chroma_block_pred2(const uint8_t* __restrict__ cb, const uint8_t* __res
     // (4..7)}; byte 3 reads zero
     uint32_t sel = 0x0c000000u;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) sel |= (uint32_t)(clip3(0, W - 1, xi + c) - a) << (8 * c);
+    for (int c = 0; c < 3; ++c) sel |= (uint32_t)(clip0(W - 1, xi + c) - a) << (8 * c);
     const u16x2 wa = (u16x2)(unsigned short)((8 - xf) * (8 - yf)), wb = (u16x2)(unsigned short)(xf * (8 - yf));
     const u16x2 wc = (u16x2)(unsigned short)((8 - xf) * yf), wd = (u16x2)(unsigned short)(xf * yf);
 #pragma unroll

@@ -13,7 +13,8 @@ timeout -s KILL 120 rocprofv3 --kernel-trace --stats --output-format csv -d "$OU
 i=0
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" \
            "FETCH_SIZE" "WRITE_SIZE" \
-           "SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_INSTS_SMEM GRBM_GUI_ACTIVE"; do
+           "SQ_INSTS_VMEM_WR SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES SQ_INSTS_SMEM GRBM_GUI_ACTIVE" \
+           "SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES"; do    # one pass: their ratio / 4 = resident waves per SIMD (pmc_summary.py)
   i=$((i+1))
   timeout -s KILL 90 rocprofv3 --pmc $grp --output-format csv -d "$OUT/pmc$i" -o run -- python3 "$ROOT/bench.py" $ARGS > "$OUT/pmc$i.log" 2>&1
 done

@@ -31,6 +31,14 @@ for k, cs in vals.items():
         m = sum(v) / len(v)
         extra = f"   per MB {m / a.mbs:12.2f}" if a.mbs else ""
         print(f"  {c:24s} {m:16.1f}{extra}")
+    if cs.get("SQ_BUSY_CU_CYCLES") and cs.get("SQ_WAVE_CYCLES"):
+        # waves resident per SIMD of the busy CUs: SQ_WAVE_CYCLES counts quad-cycles summed over waves,
+        # SQ_BUSY_CU_CYCLES on gfx950 cycles summed over CUs (per CU it equals GRBM_GUI_ACTIVE per XCD),
+        # 4 SIMDs per CU: w * 4 / cu / 4
+        w = sum(cs["SQ_WAVE_CYCLES"]) / len(cs["SQ_WAVE_CYCLES"])
+        cu = sum(cs["SQ_BUSY_CU_CYCLES"]) / len(cs["SQ_BUSY_CU_CYCLES"])
+        if cu:
+            print(f"  {'resident waves / SIMD':24s} {w / cu:16.3f}")
 
 if a.json and a.mbs:
     import json
