@@ -1,7 +1,8 @@
 // host_output.hip -- the output stage of include/h264r_output.h on the host: the geometry and layout
 // of cropped, RGB, scaled and resampled RGB frames and of the images of a boxes job, the plans of the
-// resampler (its tables come from resample_tables.h), and the launches of k_output.hip / k_output_scale.hip /
-// k_output_boxes.hip / k_output_resample.hip.
+// resampler (its tables come from resample_tables.h), the planes of a deinterlaced frame
+// (include/h264r_deinterlace.h), and the launches of k_output.hip / k_output_scale.hip / k_output_boxes.hip /
+// k_output_resample.hip / k_deinterlace.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -111,6 +112,94 @@ int h264r_output_frames(h264r_ctx* c, const h264r_out_desc* desc, const h264r_ou
     const int per = h264r::OUT_THREADS * h264r::OUT_ITEMS;
     const dim3 grid((unsigned)((items + per - 1) / per), (unsigned)std::min(num_frames, 65535), (unsigned)job.nplanes);
     hipLaunchKernelGGL(k_output, grid, dim3(h264r::OUT_THREADS), 0, s, job, frames, dst, c->d_err.p);
+    HIP_OK(hipGetLastError());
+    return H264R_OK;
+}
+
+// ------------------------------------------------------------- deinterlaced frames (h264r_deinterlace.h)
+// The coded-size planes of one deinterlaced frame and the cropped rectangle inside each: for the caller as
+// an h264r_deint_geom, and as the job k_deinterlace takes.  Argument errors come before what is merely
+// unsupported.
+static int deint_plan(int fmt, const h264r_out_desc* d, h264r_deint_geom* g, h264r::DeintJob* job)
+{
+    if (!d || d->layout != H264R_OUT_PLANAR || d->pitch_align > 1 || d->fake_chroma != 0) return H264R_EINVAL;
+    h264r_out_geom og;
+    const int st = output_plan(fmt, d, &og, nullptr);
+    if (st != H264R_OK) return st;
+    const int nplanes = fmt ? 3 : 1;
+    const int32_t* const rect[3] = {og.luma, og.chroma, og.chroma};
+    for (int k = 0; k < nplanes; ++k)
+        if ((rect[k][1] | rect[k][3]) & 1) return H264R_EUNSUPPORTED;
+    const int sub_w = (fmt == 1 || fmt == 2) ? 2 : 1, sub_h = fmt == 1 ? 2 : 1;
+    const int64_t pitch[3] = {16 * (int64_t)d->width_mbs, 16 / sub_w * (int64_t)d->width_mbs, 16 / sub_w * (int64_t)d->width_mbs};
+    const int64_t rows[3] = {16 * (int64_t)d->frame_height_mbs, 16 / sub_h * (int64_t)d->frame_height_mbs,
+                             16 / sub_h * (int64_t)d->frame_height_mbs};
+    int64_t off[3] = {0, 0, 0}, frame_bytes = 0;
+    for (int k = 0; k < nplanes; ++k) { off[k] = frame_bytes; frame_bytes += pitch[k] * rows[k]; }
+    if (g) {
+        *g = h264r_deint_geom{};
+        for (int k = 0; k < nplanes; ++k) {
+            for (int i = 0; i < 4; ++i) g->rect[k][i] = rect[k][i];
+            g->plane_off[k] = off[k];
+            g->plane_pitch[k] = pitch[k];
+        }
+        g->frame_bytes = frame_bytes;
+    }
+    if (job) {
+        h264r::DeintJob J{};
+        for (int k = 0; k < nplanes; ++k) {
+            h264r::DeintPlane& p = J.pl[k];
+            p.off = off[k];
+            p.pitch = (int32_t)pitch[k];
+            p.x0 = rect[k][0]; p.y0 = rect[k][1]; p.w = rect[k][2]; p.h = rect[k][3];
+            p.tiles_x = (p.w + h264r::DEINT_TW - 1) / h264r::DEINT_TW;
+            p.tiles = p.tiles_x * ((p.h + h264r::DEINT_TH - 1) / h264r::DEINT_TH);
+            p.which = k;
+        }
+        J.nplanes = nplanes;
+        J.need_chroma = fmt != 0;
+        J.frame_stride = frame_bytes;
+        *job = J;
+    }
+    return H264R_OK;
+}
+
+int h264r_deinterlace_geometry(int chroma_format_idc, const h264r_out_desc* desc, h264r_deint_geom* geom)
+{
+    if (!geom) return H264R_EINVAL;
+    return deint_plan(chroma_format_idc, desc, geom, nullptr);
+}
+
+int h264r_deint_job_status(const h264r_deint_job* job, int num_frames)
+{
+    if (!job || num_frames < 0) return H264R_EINVAL;
+    const bool ok = job->cur >= 0 && job->cur < num_frames && job->prev >= -1 && job->prev < num_frames && job->next >= -1 &&
+                    job->next < num_frames && (job->keep == 0 || job->keep == 1) && (job->second == 0 || job->second == 1) &&
+                    (job->mode == H264R_DEINT_BOB || job->mode == H264R_DEINT_ADAPTIVE);
+    return ok ? H264R_OK : H264R_EINVAL;
+}
+
+int h264r_deinterlace(h264r_ctx* c, const h264r_out_desc* desc, const h264r_out_frame* frames, int num_frames,
+                      const h264r_deint_job* jobs, int num_jobs, uint8_t* dst, int64_t dst_frame_stride, void* stream)
+{
+    if (!c || !desc || !frames || !jobs || !dst || num_frames < 0 || num_jobs < 0) return H264R_EINVAL;
+    h264r::DeintJob job;
+    const int st = deint_plan(c->fmt, desc, nullptr, &job);
+    if (st != H264R_OK) return st;
+    if (dst_frame_stride < job.frame_stride) return H264R_EINVAL;
+    if (num_jobs == 0) return H264R_OK;
+    job.frame_stride = dst_frame_stride;
+    job.num_frames = num_frames;
+    job.num_jobs = num_jobs;
+    hipStream_t s;
+    if (const int e = output_stream(c, stream, &s)) return e;
+    int tiles = 0;
+    for (int k = 0; k < job.nplanes; ++k) tiles = std::max(tiles, job.pl[k].tiles);
+    const int gx = (tiles + h264r::DEINT_GROUP - 1) / h264r::DEINT_GROUP * h264r::DEINT_GROUP;
+    // job z / nplanes * grid.y + y, plane z % nplanes: one launch holds any number of jobs
+    const int gy = std::min(num_jobs, 16384);
+    const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)(job.nplanes * ((num_jobs + gy - 1) / gy)));
+    hipLaunchKernelGGL(k_deinterlace, grid, dim3(h264r::DEINT_THREADS), 0, s, job, frames, jobs, dst, c->d_err.p);
     HIP_OK(hipGetLastError());
     return H264R_OK;
 }

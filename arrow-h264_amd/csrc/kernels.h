@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "h264r.h"
+#include "h264r_deinterlace.h"
 #include "h264r_output.h"
 #include "launch_cfg.h"
 #include "output_job.h"
@@ -75,7 +76,7 @@ enum DevErr : int {
     // MBAFF: what that launch sequence does not decode, k_mbaff.hip (OR-ed by k_mbaff_inter)
     DEV_ERR_MBAFF_REFUSED = 8,
     // a refused output frame (OR-ed by k_output, k_output_rgb, k_output_rgb_scaled, k_output_rgb_resampled), a refused box
-    // (OR-ed by k_output_boxes_plan)
+    // (OR-ed by k_output_boxes_plan), a refused deinterlacing job (OR-ed by k_deinterlace)
     DEV_ERR_OUTPUT = 16,
 };
 
@@ -158,3 +159,7 @@ H264R_SCALE_KERNELS(H264R_BOXES_KERNEL_DECL)
 #define H264R_RESAMPLE_KERNEL_DECL(NAME, MODE) \
     extern "C" __global__ void k_output_rgb_resampled_##NAME(h264r::ResampleJob job, const h264r_out_frame* frames, uint8_t* dst, int* err);
 H264R_RESAMPLE_KERNELS(H264R_RESAMPLE_KERNEL_DECL)
+// k_deinterlace.hip: deinterlaced frames (h264r_deinterlace.h), every job and plane in one launch
+static_assert(h264r::DEINT_TW == H264R_DEINT_TILE_W && h264r::DEINT_TH == H264R_DEINT_TILE_H, "the header names the kernel's tile");
+extern "C" __global__ void k_deinterlace(h264r::DeintJob job, const h264r_out_frame* frames, const h264r_deint_job* jobs, uint8_t* dst,
+                                         int* err);

@@ -168,4 +168,35 @@ constexpr int RS_STRIP_MAX = ((RS_TW - 1) * 48 + 97 + 1 + 15) / 16 * 16;
 static_assert(4 * (RS_TW + RS_TH) * RS_MAX_TAPS + 4 * 2 * (RS_TW + RS_TH) + ((RS_SPAN_MAX * 3 * RS_TW + 15) & ~15) + 4 * RS_STRIP_MAX +
               3 * RS_TH * RS_TW + 4 * RS_OUT_WORDS <= RS_LDS_MAX, "the widest job fits with one row a step");
 
+// What h264r_deinterlace hands k_deinterlace (k_deinterlace.hip): per plane, the cropped rectangle inside
+// the coded plane (the same in every source and in the output frame, whose planes are coded-size too) and
+// how it is cut into tiles; the sizes of the two device tables.
+constexpr int DEINT_THREADS = 64;         // threads per workgroup: one wave
+constexpr int DEINT_UNIT = 16;            // columns a lane owns: one 16-byte store per output row
+constexpr int DEINT_TW = 32;              // H264R_DEINT_TILE_W: DEINT_TW / DEINT_UNIT lanes side by side
+constexpr int DEINT_TH = 64;              // H264R_DEINT_TILE_H: DEINT_TH / 2 field rows, one per lane
+constexpr int DEINT_GROUP = 32;           // the grid's x is a multiple of it: deint_tile()'s permutation
+static_assert(DEINT_TW / DEINT_UNIT * (DEINT_TH / 2) == DEINT_THREADS, "a lane per unit and field row of a tile");
+
+struct DeintPlane {
+    int64_t off;               // inside the output frame, bytes
+    int32_t pitch;             // coded width: of the sources' planes and of the output's
+    int32_t x0, y0, w, h;      // the cropped rectangle; y0 and h are even
+    int32_t tiles_x, tiles;    // tiles in a row of tiles, and in all
+    int32_t which;             // 0 y, 1 u, 2 v of an h264r_out_frame
+};
+
+struct DeintJob {
+    DeintPlane pl[3];
+    int32_t nplanes;
+    int32_t need_chroma;       // 0 on a 4:0:0 context: u / v are neither tested nor read
+    int32_t num_frames, num_jobs;
+    int64_t frame_stride;
+};
+
+// The tile block b of a launch takes.  Blocks b and b + 8 are observed to share an XCD and its L2; a tile
+// is a quarter of a 128-byte line wide, so the four tiles of a line go to blocks 8 apart.  A permutation
+// of every aligned group of DEINT_GROUP blocks, and only a matter of speed.
+inline __host__ __device__ int deint_tile(int b) { return (b & ~31) | ((b & 7) << 2) | ((b >> 3) & 3); }
+
 }  // namespace h264r

@@ -461,9 +461,97 @@ def letterbox_boxes(n: int, lw: int, lh: int, image_w: int, image_h: int) -> np.
     return tab
 
 
+# --------------------------------------------------------------------------------------------
+# Deinterlaced frames (include/h264r_deinterlace.h, h264r_deinterlace).
+DEINT_BOB, DEINT_ADAPTIVE = 0, 1                                  # h264r_deint_job.mode
+DEINT_TILE_W, DEINT_TILE_H = 32, 64                               # H264R_DEINT_TILE_W / _H: the kernel's tile of samples
+
+# h264r_deint_job: cur, prev, next, keep, second, mode
+DEINT_JOB_DTYPE = np.dtype([("cur", "<i4"), ("prev", "<i4"), ("next", "<i4"), ("keep", "<i4"), ("second", "<i4"),
+                            ("mode", "<i4")])
+assert DEINT_JOB_DTYPE.itemsize == 24
+
+
+class DeintJob(C.Structure):
+    """h264r_deint_job"""
+    _fields_ = [("cur", C.c_int32), ("prev", C.c_int32), ("next", C.c_int32), ("keep", C.c_int32), ("second", C.c_int32),
+                ("mode", C.c_int32)]
+
+
+class DeintGeom(C.Structure):
+    """h264r_deint_geom"""
+    _fields_ = [("rect", (C.c_int32 * 4) * 3), ("plane_off", C.c_int64 * 3), ("plane_pitch", C.c_int64 * 3),
+                ("frame_bytes", C.c_int64)]
+
+
+@dataclass(frozen=True)
+class DeintGeometry:
+    """h264r_deint_geom: the cropped rectangle inside each coded-size plane and the layout of one frame."""
+    rect: tuple
+    plane_off: tuple[int, int, int]
+    plane_pitch: tuple[int, int, int]
+    frame_bytes: int
+
+
+def deint_geometry(desc: OutDesc, chroma_format: int = 1) -> DeintGeometry:
+    """h264r_deinterlace_geometry (host only, no GPU): raises H264RError with the library's status."""
+    from . import _check, lib
+    g = DeintGeom()
+    _check("h264r_deinterlace_geometry", lib().h264r_deinterlace_geometry(chroma_format, C.byref(desc), C.byref(g)))
+    return DeintGeometry(tuple(tuple(r) for r in g.rect), tuple(g.plane_off), tuple(g.plane_pitch), int(g.frame_bytes))
+
+
+def deint_job_table(jobs) -> np.ndarray:
+    """A host job table (DEINT_JOB_DTYPE) of `jobs`: such an array already, or an iterable of jobs, each a
+    mapping or a sequence (cur, prev, next, keep, second, mode)."""
+    if isinstance(jobs, np.ndarray) and jobs.dtype == DEINT_JOB_DTYPE:
+        return np.ascontiguousarray(jobs.reshape(-1))
+    rows = list(jobs)
+    tab = np.zeros(len(rows), DEINT_JOB_DTYPE)
+    for i, row in enumerate(rows):
+        if hasattr(row, "keys"):
+            for k in row.keys():
+                tab[i][k] = row[k]
+        else:
+            if len(row) != 6:
+                raise ValueError("a job is (cur, prev, next, keep, second, mode)")
+            for k, v in zip(DEINT_JOB_DTYPE.names, row):
+                tab[i][k] = int(v)
+    return tab
+
+
+def deint_job_status(job, num_frames: int) -> int:
+    """h264r_deint_job_status (host only, no GPU) of one job -- a DeintJob, or one row of a job table: the
+    library's status, H264R_OK for a record the device accepts."""
+    from . import lib
+    if not isinstance(job, DeintJob):
+        job = DeintJob.from_buffer_copy(deint_job_table([job] if not isinstance(job, np.ndarray) else job)[:1].tobytes())
+    return int(lib().h264r_deint_job_status(C.byref(job), num_frames))
+
+
+def deint_jobs(n_frames: int, tff: bool = True, mode: int = DEINT_ADAPTIVE, field_rate: bool = False) -> np.ndarray:
+    """The usual job table for n_frames interlaced frames in display order, tff: the top field is the
+    first in time.  At frame rate one job per frame, keeping its first field; at field rate two, the first
+    field (second 0) and then the other (second 1).  prev is -1 at the start, next -1 at the end."""
+    first = 0 if tff else 1
+    per = 2 if field_rate else 1
+    tab = np.zeros(n_frames * per, DEINT_JOB_DTYPE)
+    for i in range(n_frames):
+        for s in range(per):
+            tab[i * per + s] = (i, i - 1 if i else -1, i + 1 if i + 1 < n_frames else -1, first ^ s, s, mode)
+    return tab
+
+
 def bind(L) -> None:
-    """Declare the prototypes of include/h264r_output.h on the library (h264r.lib())."""
+    """Declare the prototypes of include/h264r_output.h and include/h264r_deinterlace.h on the library
+    (h264r.lib())."""
     P, I = C.c_void_p, C.c_int
+    L.h264r_deinterlace_geometry.argtypes = [I, C.POINTER(OutDesc), C.POINTER(DeintGeom)]
+    L.h264r_deinterlace_geometry.restype = I
+    L.h264r_deint_job_status.argtypes = [C.POINTER(DeintJob), I]
+    L.h264r_deint_job_status.restype = I
+    L.h264r_deinterlace.argtypes = [P, C.POINTER(OutDesc), P, I, P, I, P, C.c_int64, P]
+    L.h264r_deinterlace.restype = I
     L.h264r_output_geometry.argtypes = [I, C.POINTER(OutDesc), C.POINTER(OutGeom)]
     L.h264r_output_geometry.restype = I
     L.h264r_output_frames.argtypes = [P, C.POINTER(OutDesc), P, I, P, C.c_int64, P]
@@ -696,6 +784,67 @@ class DeviceOutput:
                self.decoder._L.h264r_output_rgb_resampled(self.decoder.handle, plan.handle, C.c_void_p(tptr), n,
                                                           C.c_void_p(dst.data_ptr()), dst.stride(0), C.c_void_p(stream or 0)))
         return rgb_view(dst[:n], g, plan.format)
+
+    def deinterlace(self, table, jobs, dst=None, stream: int | None = None, *, n: int | None = None,
+                    num_jobs: int | None = None):
+        """h264r_deinterlace on the same frame table: one progressive frame per job of `jobs` -- a host
+        table (deint_job_table's input: a DEINT_JOB_DTYPE array such as deint_jobs() returns, or an iterable
+        of jobs), uploaded here; or a torch uint8 tensor on the device that holds h264r_deint_job records;
+        or a raw device address with num_jobs.  Needs this geometry planar, without pitch_align and
+        fake_chroma.  Returns the torch uint8 tensor [num_jobs, frame_bytes] of coded-size planes (dst, if
+        given: [num_jobs, dst_frame_stride], of which only the cropped rectangles are written; None = a new
+        ZERO-FILLED one); frames_of() names its frames to the other calls.  Asynchronous on `stream`, as
+        run()."""
+        import torch
+        from . import _check
+        if isinstance(table, FrameTable):
+            n = table.n if n is None else n
+            tptr = table.tensor.data_ptr()
+        else:
+            tptr = self._addr(table)
+        if n is None:
+            raise ValueError("deinterlace: n is needed with a raw frame table")
+        keep = None
+        if hasattr(jobs, "data_ptr"):
+            if jobs.dtype != torch.uint8 or not jobs.is_contiguous() or jobs.numel() % DEINT_JOB_DTYPE.itemsize:
+                raise ValueError("deinterlace: a device job table is a contiguous uint8 tensor of 24-byte records")
+            num_jobs = jobs.numel() // DEINT_JOB_DTYPE.itemsize if num_jobs is None else num_jobs
+            jptr = jobs.data_ptr()
+        elif isinstance(jobs, int):
+            if num_jobs is None:
+                raise ValueError("deinterlace: num_jobs is needed with a raw job table")
+            jptr = jobs
+        else:
+            tab = deint_job_table(jobs)
+            num_jobs = len(tab) if num_jobs is None else num_jobs
+            # one record more than the table holds: an empty table still has an address
+            raw = np.concatenate([tab.view(np.uint8).reshape(-1), np.zeros(DEINT_JOB_DTYPE.itemsize, np.uint8)])
+            keep = torch.from_numpy(raw).to("cuda")
+            jptr = keep.data_ptr()
+        g = deint_geometry(self.desc, self.chroma_format)
+        if dst is None:
+            dst = torch.zeros((num_jobs, g.frame_bytes), dtype=torch.uint8, device="cuda")
+        if dst.dim() != 2 or dst.shape[0] < num_jobs or dst.stride(1) != 1 or dst.dtype != torch.uint8:
+            raise ValueError("deinterlace: dst must be a uint8 tensor [num_jobs, dst_frame_stride] with contiguous rows")
+        _check("h264r_deinterlace",
+               self.decoder._L.h264r_deinterlace(self.decoder.handle, C.byref(self.desc), C.c_void_p(tptr), n, C.c_void_p(jptr),
+                                                 num_jobs, C.c_void_p(dst.data_ptr()), dst.stride(0), C.c_void_p(stream or 0)))
+        if keep is not None:
+            self._deint_tables = [keep]                     # alive until the next call replaces it
+        return dst[:num_jobs]
+
+    def frames_of(self, view) -> FrameTable:
+        """The frame table that names the frames of deinterlace()'s result -- `view`, [n, stride] -- as
+        H264R_OUT_FRAME sources for run(), rgb() and the other calls of this geometry."""
+        g = deint_geometry(self.desc, self.chroma_format)
+        if view.dim() != 2 or view.stride(1) != 1 or view.shape[1] < g.frame_bytes:
+            raise ValueError("frames_of: view must be deinterlace()'s [n, dst_frame_stride] tensor")
+        base, stride = view.data_ptr(), view.stride(0)
+        rows = [(OUT_FRAME, tuple(base + i * stride + g.plane_off[k] if k == 0 or self.chroma_format else None for k in range(3)))
+                for i in range(view.shape[0])]
+        table = self.frames_from(rows)
+        table.keep.append(view)
+        return table
 
     def rgb_boxes(self, table, boxes, image_w: int, image_h: int, num_images: int, *, n: int | None = None,
                   num_boxes: int | None = None, max_out=None, filter: int = SCALE_AREA, matrix: int = CSC_BT709,

@@ -143,6 +143,8 @@ int h264r_output_frames(h264r_ctx* ctx, const h264r_out_desc* desc, const h264r_
  *     Indices clamp to the CROPPED chroma rectangle: no sample outside the crop has any influence.  The
  *     interpolation runs over the woven frame and treats it as progressive: the vertical taps of a
  *     field pair come from the two fields, those of an unpaired field mix the field with the 128 rows.
+ *     (Where the fields differ in time, h264r_deinterlace of h264r_deinterlace.h makes progressive
+ *     frames of them first; its result is named here as an H264R_OUT_FRAME source.)
  *   4:0:0 context:       C8 = 1024.
  *
  * The matrix.  All arithmetic 32-bit signed, >> an arithmetic shift, clip255(v) = min(max(v, 0), 255):
