@@ -50,12 +50,15 @@
 #ifndef H264R_INTER_FAST
 #define H264R_INTER_FAST 3
 #endif
-// H264R_INTER_MC: two shorter forms around the motion compensation, each with the form before it as the other
+// H264R_INTER_MC: shorter forms around the motion compensation, each with the form before it as the other
 // side of an `if constexpr`, so that either builds from one tree for an A/B (make EXTRA=-DH264R_INTER_MC=<bits>):
 // 1 the luma and chroma window fetches clamp rows and columns by one v_med3_i32 (clip0), 2 inter4_lane divides
-// in 24 bits.  What else was tried in luma_block_pred and why it is not here: profiles/r12_a_inter_mc_wg_ab.txt.
+// in 24 bits, 4 a luma window across the left or right edge is fixed up once, in a block that a wave without such a
+// lane skips (luma_window_edge), and the row loop of luma_block_pred has no branch (the PLAIN stages only: the
+// generic ones spill with it).  What else was tried in
+// luma_block_pred and why it is not here: profiles/r12_a_inter_mc_wg_ab.txt.
 #ifndef H264R_INTER_MC
-#define H264R_INTER_MC 3
+#define H264R_INTER_MC 7
 #endif
 
 namespace h264r {
@@ -362,12 +365,60 @@ DEV void luma_window_global(const uint8_t* __restrict__ img, int W, int pitch, i
 // branch, which had steered k_inter4r's register allocation: each output row is finished as
 // soon as its last tap row is in, so its accumulators are free for the rest of the window and
 // the kernel fits 128 VGPRs without it.)
-DEV void luma_block_pred(const uint32_t (&w)[9][3], int W, int x, int xf, int yf, uint32_t (&out)[4])
+// A window that crosses the picture's left or right edge, rewritten in place (H264R_INTER_MC bit 2): row r's
+// dwords become the clamped samples 0..3, 4..7 and 8 (byte 0), which is what the interior extraction of
+// luma_block_pred gives at shift 0.  The clamped column k sits at byte idx[k] = clip(x - 2 + k) - a of the row's
+// 12 bytes; idx never steps by more than one, so samples 0..3 lie in one pair of neighbouring dwords and samples
+// 4..8 in one: a byte permute each, the selectors and the pairs chosen once per lane (chroma_block_pred2's way).
+// The caller runs it under its lane's !inside: a wave with no such lane skips it whole, column clamps included.
+DEV void luma_window_edge(uint32_t (&w)[9][3], int W, int x)
 {
+    // opaque to the compiler, so that the column arithmetic is not moved out in front of the caller's branch,
+    // where every wave would execute it
+    asm volatile("" : "+v"(x));
+    const int a = clip0(W - 1, x - 2) & ~3;
+    int idx[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) idx[k] = clip0(W - 1, x - 2 + k) - a;      // 0 .. 11
+    const bool hi0 = idx[0] >= 4, hi1 = idx[4] >= 4;                       // the pair is dwords {1, 2}, not {0, 1}
+    const int o0 = hi0 ? 4 : 0, o1 = hi1 ? 4 : 0;
+    uint32_t sel0 = 0, sel1 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        sel0 |= (uint32_t)(idx[k] - o0) << (8 * k);
+        sel1 |= (uint32_t)(idx[4 + k] - o1) << (8 * k);
+    }
+    const uint32_t sel2 = 0x0c0c0c00u | (uint32_t)(idx[8] - o1);
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+        const uint32_t lo0 = hi0 ? w[r][1] : w[r][0], up0 = hi0 ? w[r][2] : w[r][1];
+        const uint32_t lo1 = hi1 ? w[r][1] : w[r][0], up1 = hi1 ? w[r][2] : w[r][1];
+        w[r][0] = __builtin_amdgcn_perm(up0, lo0, sel0);
+        w[r][1] = __builtin_amdgcn_perm(up1, lo1, sel1);
+        w[r][2] = __builtin_amdgcn_perm(up1, lo1, sel2);
+    }
+}
+
+// w: not const -- an edge lane's window is rewritten in place (luma_window_edge).
+// ONCE: bit 2 of H264R_INTER_MC applies (the PLAIN stages).  The generic stages keep the per-row form: without the
+// per-row branches their nine rows are one basic block, which the scheduler interleaves past k_inter4r's 96 VGPRs
+// (6 spilled; 1 with a scheduling barrier per row: profiles/r13_a_inter_edge_isa.txt).
+template <bool ONCE>
+DEV void luma_block_pred(uint32_t (&w)[9][3], int W, int x, int xf, int yf, uint32_t (&out)[4])
+{
+    constexpr int MC = ONCE ? H264R_INTER_MC : (H264R_INTER_MC & ~4);
     const int hs = xf == 3 ? 1 : 0;                  // G / h column c + 2 + hs
     const int brow = yf == 3 ? 1 : 0;                // b / G row i + 2 + brow
     const bool inside = x - 2 >= 0 && x + 6 < W;
-    const int sh = (x - 2) & 3;
+    int sh = (x - 2) & 3;
+    if constexpr (MC & 4) {
+        // the edge lanes fix their window up once, here; the row loop below is then the interior extraction
+        // for every lane, with no branch in it
+        if (!inside) {
+            luma_window_edge(w, W, x);
+            sh = 0;
+        }
+    }
     // output = (X + Y + 1) >> 1, X, Y in {0 G, 1 b, 2 h, 3 j}: (xs, ys) of the 16 phases as a
     // 64-bit table (an if-chain on the lane's phase compiled to lane-divergent branches)
     // XSYS nibble 4 xf + yf = xs | ys << 2:  xf 0: (0,0) (0,2) (2,2) (0,2); yf 0: (0,1) (1,1)
@@ -397,7 +448,7 @@ DEV void luma_block_pred(const uint32_t (&w)[9][3], int W, int x, int xf, int yf
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
         uint32_t r0, r1, r2;
-        if (inside) {
+        if ((MC & 4) || inside) {
             r0 = __builtin_amdgcn_alignbyte(w[r][1], w[r][0], sh);
             r1 = __builtin_amdgcn_alignbyte(w[r][2], w[r][1], sh);
             r2 = w[r][2] >> (8 * sh);
@@ -782,6 +833,7 @@ DEV void inter4_pcm(uint8_t* rmb, const Inter4Lane& L, const int16_t* lv)
 // row i's four samples as bytes, tC[pl] my 2x2 chroma samples of plane pl (chroma_block_pred2); 128
 // (no_ref, inter_prediction.cc:164-167,366-369) where the list's entry names no picture.  `use`: the
 // lane predicts from this list at all.  structure / fld: the picture's, wave-uniform.
+template <bool PLAIN>
 DEV void inter4_mc(const Geom& g, const Inter4Lane& L, const Inter4Lds& S, int structure, int fld, uint2 mw, int rr, bool use,
                    uint32_t (&tY)[4], uint32_t (&tC)[2])
 {
@@ -811,7 +863,7 @@ DEV void inter4_mc(const Geom& g, const Inter4Lane& L, const Inter4Lds& S, int s
                     tY[0] = tY[1] = tY[2] = tY[3] = acc;
                 }
             } else {
-                if (ok) luma_block_pred(w, g.W, x, vx & 3, vy & 3, tY);
+                if (ok) luma_block_pred<PLAIN>(w, g.W, x, vx & 3, vy & 3, tY);
             }
         }
     }
@@ -843,7 +895,7 @@ DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inte
     const int fld = structure != H264R_FRAME;
     const int r0 = (int8_t)(m0.y & 255);
     if constexpr (PLAIN) {
-        inter4_mc(g, L, S, structure, fld, m0, r0, true, predY, predC);
+        inter4_mc<true>(g, L, S, structure, fld, m0, r0, true, predY, predC);
         return;
     }
     const int r1 = (int8_t)(m1.y & 255);
@@ -865,7 +917,7 @@ DEV void inter4_predict(const h264r_batch& b, const Geom& g, int pic, const Inte
         if constexpr (PARK)
             if (l) mw = make_uint2(park_get(*park, PARK_M1), park_get(*park, PARK_M1 + 1));
         uint32_t tY[4], tC[2];
-        inter4_mc(g, L, S, structure, fld, mw, rr, use, tY, tC);
+        inter4_mc<false>(g, L, S, structure, fld, mw, rr, use, tY, tC);
         const bool l1 = l != 0;
         if constexpr (PARK) {
             // each list's prediction goes to LDS as it is finished and both come back after the loop:

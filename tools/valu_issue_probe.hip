@@ -44,6 +44,21 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
         if (s == 0x12345678u) out[threadIdx.x] = (uint32_t)s;                                                 \
     }
 
+// a 64-bit accumulator as two halves plus a temporary, for the sequences that replace one 64-bit instruction
+#define KERNEL64S(NAME, ASM)                                                                                  \
+    __global__ __launch_bounds__(256, 5) void NAME(uint32_t* out, uint32_t x, uint32_t y)                      \
+    {                                                                                                         \
+        uint32_t lo[8], hi[8], t[8], b = x + threadIdx.x, c = y ^ threadIdx.x;                                \
+        for (int k = 0; k < 8; ++k) { lo[k] = x * (k + 1) + threadIdx.x; hi[k] = y + k; t[k] = k; }           \
+        for (int i = 0; i < ITER; ++i) {                                                                      \
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) asm volatile(ASM : "+v"(lo[k]), "+v"(hi[k]), "+v"(t[k]) : "v"(b), "v"(c) : "vcc"); \
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) asm volatile(ASM : "+v"(lo[k]), "+v"(hi[k]), "+v"(t[k]) : "v"(b), "v"(c) : "vcc"); \
+        }                                                                                                     \
+        uint32_t s = 0;                                                                                       \
+        for (int k = 0; k < 8; ++k) s ^= lo[k] ^ hi[k] ^ t[k];                                                \
+        if (s == 0x12345678u) out[threadIdx.x] = s;                                                           \
+    }
+
 KERNEL32(k_fma_f32, "v_fma_f32 %0, %0, %1, %2")
 KERNEL32(k_add_u32, "v_add_u32 %0, %0, %1")
 KERNEL32(k_pk_add_u16, "v_pk_add_u16 %0, %0, %1")
@@ -77,6 +92,8 @@ KERNEL64(k_pk_fma_f32, "v_pk_fma_f32 %0, %0, %1, %2")
 KERNEL64(k_pk_add_f32, "v_pk_add_f32 %0, %0, %1")
 KERNEL64(k_mad_i64_i32, "v_mad_i64_i32 %0, vcc, %3, %4, %0")
 KERNEL64(k_lshl_add_u64, "v_lshl_add_u64 %0, %0, 0, %1")
+// what would replace v_mad_i64_i32 in an address: a 24-bit product added to a 64-bit base (three instructions per slot)
+KERNEL64S(k_mul_u24_add_u64, "v_mul_u32_u24 %2, %3, %4\n v_add_co_u32 %0, vcc, %0, %2\n v_addc_co_u32 %1, vcc, 0, %1, vcc")
 
 struct Probe {
     const char* name;
@@ -99,7 +116,7 @@ int main()
                             P(k_max_i32), P(k_lshlrev_b32), P(k_bitop3), P(k_cmp_cndmask), P(k_bfi_b32), P(k_med3_f32), P(k_med3_i32),
                             P(k_cvt_i32_f32), P(k_cvt_f32_i32_sdwa), P(k_dot2_i32_i16), P(k_mad_u32_u24), P(k_mad_i32_i24),
                             P(k_mul_lo_u32), P(k_sad_u32), P(k_lshl_or_b32), P(k_mov_dpp), P(k_pk_fma_f32), P(k_pk_add_f32),
-                            P(k_mad_i64_i32), P(k_lshl_add_u64)};
+                            P(k_mad_i64_i32), P(k_lshl_add_u64), P(k_mul_u24_add_u64)};
     // 5 workgroups of 4 waves per CU: 5 waves per SIMD, three rounds of them
     const dim3 grid(cus * 5 * 3), block(256);
     double base = 0;
